@@ -31,10 +31,21 @@ training runs the reference's batch per rank with one all-reduce of the
 gradient bucket per step. The timed region is bracketed by barrier +
 synchronize and the max over ranks is reported.
 
-rank 0 prints ONE JSON line: the metric, ``roofline`` for the dominant kernel
-(algorithmic work / its average duration, timed live with HIP events on the
-stream the kernels run on), ``roofline_other`` for the other stages, and a
-``cpu_baseline`` (the oracle's CPU path on a bounded sample, N = 1 only).
+rank 0 prints ONE JSON line. A plain run does only what the headline needs:
+setup, W warmup steps, K timed steps, then the metric (``value``, ``unit``,
+``ms_per_step``, ...). ``--dump-outputs DIR`` also writes what the last timed
+step computed as DIR/<name>.npy (float32 / float64, a fixed seeded sample of
+the rows of a large array; every host and device generator is seeded, so the
+same arguments give the same inputs from run to run).
+
+``--full`` adds everything else to the same line: ``roofline`` for the dominant
+kernel (algorithmic work / its average duration, timed live with HIP events on
+the stream the kernels run on; for the pipelined headline in sequential steps
+of their own), ``roofline_other`` for the other stages and the untimed kernel
+variants, a ``cpu_baseline`` (the oracle's CPU path on a bounded sample, N = 1
+only), ``configs_other`` (configs 2, 3, 4 and 1 after the headline), config 4's
+``cli_path``, the N > 1 ``faithful_global_batch`` mode and config 2's one-off
+equality check against SpeechEmbeddings.featurize.
 """
 from __future__ import annotations
 
@@ -66,6 +77,15 @@ def parse():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", type=int, default=5, choices=(1, 2, 3, 4, 5))
+    ap.add_argument("--full", action="store_true",
+                    help="beside the metric: per-stage rooflines (for config 5 from sequential steps of their own), "
+                         "the untimed kernel variants, the CPU baseline, configs_other, config 4's cli_path, the "
+                         "N > 1 faithful_global_batch mode and config 2's equality check (the options that tune "
+                         "these only act with --full)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (rank 0's arrays) as "
+                         "DIR/<name>.npy, float32 / float64, at most 64 MB in all: of an array above its share "
+                         "a fixed seeded sample of rows")
     ap.add_argument("--clips", type=int, default=100_000, help="clips per rank per step (configs 2, 3, 5)")
     ap.add_argument("--cpu-sample", type=int, default=None, help="units timed on the host CPU (~10-30 s)")
     ap.add_argument("--no-cpu", action="store_true")
@@ -201,6 +221,94 @@ def prof_mark(tag, dev):
     torch.cuda.synchronize(dev)
 
 
+def seed_everything(seed):
+    """Every generator a setup or a step draws from without naming one: Python's
+    (the trainer's dropout seed base), numpy's global one (the augmentation
+    plan's host draws) and torch's default CPU and device generators (the batch
+    sampler's permutations). The same arguments then give the same inputs."""
+    import random
+    import numpy as np
+    random.seed(seed)
+    np.random.seed(seed % (1 << 32))
+    torch.manual_seed(seed)
+
+
+DUMP_BUDGET_BYTES = 60 << 20  # of the 64 MB a dump may hold
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: arrays (name -> tensor or ndarray, what the last timed
+    step computed) as path/<name>.npy. Floating-point arrays as float32 (float64
+    stays float64), anything else as float64. An array above its equal share of
+    the budget keeps a fixed sample of its rows (ascending, drawn without
+    replacement by numpy's default_rng(0): the same rows for the same shape)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        if a is None:  # no step ran (--steps 0 --warmup 0): nothing was computed
+            continue
+        t = (a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a))).detach()
+        if t.dim() == 0:
+            t = t.reshape(1)
+        wide = t.dtype == torch.float64 or not t.dtype.is_floating_point
+        row = max(1, t.numel() // max(1, t.shape[0]))  # elements per row (an array without rows is written as it is)
+        keep = max(1, share // (row * (8 if wide else 4)))
+        if t.shape[0] > keep:
+            rows = np.sort(np.random.default_rng(0).choice(t.shape[0], size=keep, replace=False))
+            t = t[torch.from_numpy(rows).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.to(torch.float64 if wide else torch.float32).cpu().numpy())
+
+
+def bench_checkpoint_dir():
+    """A checkpoint directory of this process's own, removed at exit."""
+    import atexit
+    import shutil
+    import tempfile
+    d = tempfile.mkdtemp(prefix="hb_bench_ck_")
+    atexit.register(shutil.rmtree, d, ignore_errors=True)
+    return d
+
+
+PROBE_STEPS = 8
+
+
+def train_probe(dev, seed, idx, y, sched, pool32, pool16, stream=None):
+    """--dump-outputs, the train step's part: the first PROBE_STEPS rows of idx / sched
+    trained on the given pools by a classifier of its own (initial weights and dropout seed
+    base seeded here), on ``stream`` (the timed path's train stream, so the same kernels
+    run); its history rows (n_sel, accumulation steps, fired, loss, n_neg_sel, fp_sel,
+    n_pos_sel, tp_sel per step) and its parameters after them.
+
+    The timed path's own classifier is not written, because it does not repeat: its gradient
+    sums are float atomics, the high-loss filter is a discrete choice per sample and Adam
+    normalises every gradient, so the rounding noise of the first sums is chaotically
+    amplified over the 1,000 steps of every chunk. Measured on ONE build, two runs with the
+    same arguments (defaults, 20 + 5 steps, same machine): parameters relative L2 difference
+    0.69 (max |d| 1.11 of max 2.30), history rows 0.17 (per column 0.07 - 0.86; after ONE
+    chunk from the same weights and batches the first 10 rows still agree to 6 digits, row 100
+    by 4 %, parameters max |d| 0.18 of 1.27). Over PROBE_STEPS steps from fixed weights the
+    same noise stays near rounding, so a train kernel that is dropped, cut short or run at a
+    lower precision shows here."""
+    import contextlib
+    import random
+    from heybuddy.trainer import WakeWordTrainer
+    torch.manual_seed(seed + 100)
+    random.seed(seed + 101)
+    tr = WakeWordTrainer(checkpoint_dir=bench_checkpoint_dir(), device=dev)
+    tr.model.train()
+    k = min(PROBE_STEPS, int(idx.shape[0]))
+    sch = sched[:k].clone()
+    sch[:, 1] = 1.0
+    hist = torch.zeros((k, 8), dtype=torch.float32, device=dev)
+    torch.cuda.synchronize(dev)
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        tr._reset_accumulation()
+        tr.train_indexed(idx[:k].contiguous(), y, sch, pool32=pool32, pool16=pool16, history=hist, steps_per_graph=k)
+    torch.cuda.synchronize(dev)
+    return {"train_probe_history": hist, "train_probe_parameters": tr.model.flat_parameters.clone()}
+
+
 def launch_ranks(args) -> int:
     """`bench.py --gpus N` run directly (no WORLD_SIZE in the environment):
     start N ranks under torch.distributed.run as a CHILD process and return
@@ -241,10 +349,13 @@ def measure(args, dev, rank, world, marks=True) -> dict:
     CURRENT_CONFIG[0] = args.config
     mark = prof_mark if marks else (lambda tag, dev: None)
     setup = {2: setup_featurize, 3: setup_featurize, 4: setup_train, 5: setup_e2e}[args.config]
-    job = setup(args, dev, rank, world, seed_for(args.config, rank))
+    seed = seed_for(args.config, rank)
+    seed_everything(seed)
+    job = setup(args, dev, rank, world, seed)
 
-    staged = job.get("staged_step")  # overlapped stages: timed per stage in separate sequential steps
-    n_ev = args.stage_steps if staged else args.steps
+    # --full: the stages are timed by events, overlapped ones in separate sequential steps
+    staged = job.get("staged_step") if args.full else None
+    n_ev = 0 if not args.full else args.stage_steps if staged else args.steps
     evs = [[torch.cuda.Event(enable_timing=True) for _ in range(len(job["stages"]) + 1)] for _ in range(n_ev)]
     if staged:  # before the pipelined warmup, which leaves the next chunk's features pending
         staged(None)
@@ -262,7 +373,7 @@ def measure(args, dev, rank, world, marks=True) -> dict:
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     for k in range(args.steps):
-        job["step"](None if staged else evs[k])
+        job["step"](None if staged or not args.full else evs[k])
     torch.cuda.synchronize(dev)
     if world > 1:
         dist.barrier()
@@ -272,20 +383,26 @@ def measure(args, dev, rank, world, marks=True) -> dict:
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
-    stage_ms = [sum(e[i].elapsed_time(e[i + 1]) for e in evs) / n_ev for i in range(len(job["stages"]))]
-    if "rooflines" in job:  # per kernel group (sub-stages timed on their own); the dominant one leads
-        roofs = job["rooflines"](dict(zip(job["stages"], stage_ms)), args.pmc)
-    else:
-        roofs = [job["roofline"](name, ms, args.pmc) for name, ms in zip(job["stages"], stage_ms)]
-    # the dominant kernel group by device time (a stage summary that only aggregates
-    # groups listed on their own is never the headline entry)
-    dom = max(range(len(roofs)), key=lambda i: (not roofs[i].get("summary"), roofs[i]["ms_per_step"]))
+    if args.dump_outputs and marks:
+        outs = job["outputs"]()  # on every rank: the train probe's steps all-reduce at N > 1
+        if rank == 0:
+            dump_outputs(args.dump_outputs, outs)
+        del outs
+    roofs, dom, extra, after, cpu = [None], 0, [], None, None
+    if args.full:
+        stage_ms = [sum(e[i].elapsed_time(e[i + 1]) for e in evs) / n_ev for i in range(len(job["stages"]))]
+        if "rooflines" in job:  # per kernel group (sub-stages timed on their own); the dominant one leads
+            roofs = job["rooflines"](dict(zip(job["stages"], stage_ms)), args.pmc)
+        else:
+            roofs = [job["roofline"](name, ms, args.pmc) for name, ms in zip(job["stages"], stage_ms)]
+        # the dominant kernel group by device time (a stage summary that only aggregates
+        # groups listed on their own is never the headline entry)
+        dom = max(range(len(roofs)), key=lambda i: (not roofs[i].get("summary"), roofs[i]["ms_per_step"]))
 
-    extra = job["extra_rooflines"]() if "extra_rooflines" in job and world == 1 else []
-    after = job["after"](elapsed / args.steps * 1e3) if "after" in job else None
-    cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
-        cpu = job["cpu_baseline"](args.cpu_sample)
+        extra = job["extra_rooflines"]() if "extra_rooflines" in job and world == 1 else []
+        after = job["after"](elapsed / args.steps * 1e3) if "after" in job else None
+        if rank == 0 and world == 1 and not args.no_cpu:
+            cpu = job["cpu_baseline"](args.cpu_sample)
     units = job["units_per_step"] * (world if job["scaling"] == "weak" else 1)
     line = {
         "metric": job["metric"], "value": round(units * args.steps / elapsed, 1), "unit": job["unit"],
@@ -293,6 +410,7 @@ def measure(args, dev, rank, world, marks=True) -> dict:
         "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": job["scaling"],
         "vs_baseline": None, "dtype": "f32", "data": job["data"], "config": job["config"], "roofline": roofs[dom],
         "roofline_other": [r for i, r in enumerate(roofs) if i != dom] + extra, "cpu_baseline": cpu,
+        "full": bool(args.full),
     }
     if after is not None:
         line["cli_path"] = after
@@ -308,7 +426,7 @@ def main():
     args = parse()
     CURRENT_CONFIG[0] = args.config
     if args.config == 1:
-        print(json.dumps(cpu_mel_only(args)), flush=True)
+        print(json.dumps(cpu_mel_only(args, dump=args.dump_outputs)), flush=True)
         return
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))
@@ -331,7 +449,7 @@ def main():
             dist.init_process_group("nccl", device_id=dev)
 
     line = measure(args, dev, rank, world)
-    if args.config == 5 and world > 1 and args.train_batch == "per-rank":
+    if args.full and args.config == 5 and world > 1 and args.train_batch == "per-rank":
         # the reference's optimisation on N GPUs: the global batch of 1,100 split over
         # the ranks, N x 1,000 steps per chunk; measured beside the weak-scaling value and named
         g = measure(sub_args(args, 5, train_batch="global"), dev, rank, world, marks=False)
@@ -341,7 +459,7 @@ def main():
             "the reference's training on N GPUs: global batch 1,100 split over the ranks (SURVEY §8e-2), "
             "N x 1,000 sequential train steps per chunk of N x 100 k clips; `value` above is the weak-scaling "
             "mode (1,100 per rank, 1,000 steps per rank)")
-    others = [int(c) for c in args.other_configs.split(",") if c.strip()] if args.config == 5 else []
+    others = [int(c) for c in args.other_configs.split(",") if c.strip()] if args.full and args.config == 5 else []
     if others:
         line["configs_other"] = []
     for c in others:  # BASELINE configs[c - 1] in the same run, after the headline
@@ -402,9 +520,11 @@ def setup_featurize(args, dev, rank, world, seed):
         i += 1
         if evs:
             evs[i].record(stream)
-        return _replace_nan_rows(emb)
+        last[0] = _replace_nan_rows(emb)
+        return last[0]
 
-    if not augment and not args.no_check:  # the step is SpeechEmbeddings.featurize; check once
+    last = [None]  # the last step's embeddings (--dump-outputs)
+    if args.full and not augment and not args.no_check:  # the step is SpeechEmbeddings.featurize; check once
         ref = SpeechEmbeddings(device_id=dev.index).featurize(clips[:64])
         assert torch.equal(ref, step(None)[:64]), "bench step diverges from SpeechEmbeddings.featurize"
 
@@ -456,7 +576,7 @@ def setup_featurize(args, dev, rank, world, seed):
 
     return {
         "step": step, "stages": stages, "roofline": roofline, "cpu_baseline": cpu_baseline,
-        "extra_rooflines": extra_rooflines,
+        "extra_rooflines": extra_rooflines, "outputs": lambda: {"embeddings": last[0]},
         "units_per_step": n, "scaling": "weak", "unit": "clips/s",
         "metric": "audio clips/sec featurized+trained, 1.5 s @16 kHz, 1/2/4/8 GPU",
         "data": "synthetic 1.5 s @16 kHz clips (seeded), SE20 stand-in embedding graph"
@@ -490,7 +610,7 @@ def setup_train(args, dev, rank, world, seed):
     pool32 = torch.cat([pos, adv])
     del pos, adv
     neg = torch.randn((200_000, 16, 96), generator=g, device=dev).half()
-    tr = WakeWordTrainer(checkpoint_dir="/tmp/hb_bench_ck", device=dev)
+    tr = WakeWordTrainer(checkpoint_dir=bench_checkpoint_dir(), device=dev)
     tr.model.train()
     STEPS_1 = 100
     # The reference's stage batches (dataset/training.py:215-231, :436-451): per dataset, positives 50,
@@ -613,9 +733,12 @@ def setup_train(args, dev, rank, world, seed):
                 "checkpoint_ms": round(ck, 3),
                 "ratio_to_train_indexed_excl_checkpoint": round((ms - ck) / ms_indexed, 3)}
 
+    def outputs():  # stage 1's first steps from fixed weights (the run's own classifier does not repeat)
+        return train_probe(dev, seed, stages[0][0], stages[0][1], stages[0][2], pool32, neg)
+
     return {
         "step": step, "stages": ["train_3stage"], "roofline": roofline, "cpu_baseline": cpu_baseline,
-        "after": cli_path,
+        "after": cli_path, "outputs": outputs,
         "units_per_step": units, "scaling": "strong", "unit": "embeddings/s",
         "metric": "wake-word classifier embeddings/sec trained (3 stages: batch 1100/550/273, steps x1/x2/x4)",
         "data": "synthetic [16,96] embedding pools in HBM (pos N(0,1)+0.5u, adv N(0,1)-0.25u, neg N(0,1) f16), "
@@ -651,7 +774,7 @@ def host_threads() -> int:
 
 
 # --------------------------------------------------------------- config 1 ----
-def cpu_mel_only(args):
+def cpu_mel_only(args, dump=None):
     """configs[0]: 1,000 synthetic clips, mel spectrogram only, on the host CPU
     (the reference's CPU path: 4 audio windows x 105 frames per clip through
     the mel graph in batches of 64, features.py:203-208). No GPU is touched.
@@ -671,6 +794,8 @@ def cpu_mel_only(args):
         el = time.perf_counter() - t0
         assert out.shape == (sub.shape[0], 420, 32)
         runs[th] = (sub.shape[0] / el, sub.shape[0], el)
+        if dump and th == threads:
+            dump_outputs(dump, {"mel": out})
     v, nn, el = runs[threads]
     line = {"metric": "audio clips/sec mel-spectrogram (CPU reference path)", "value": round(v, 1),
             "unit": "clips/s", "n_gpus": 0, "steps": 1, "warmup": 1, "ms_per_step": round(el * 1e3, 3),
@@ -767,7 +892,7 @@ def setup_e2e(args, dev, rank, world, seed):
         S = (half * world) // 50
     idx = torch.empty((S, B), dtype=torch.int32, device=dev)
     y = torch.cat([torch.ones(P), torch.zeros(B - P)]).to(dev)
-    tr = WakeWordTrainer(checkpoint_dir="/tmp/hb_bench_ck", device=dev)
+    tr = WakeWordTrainer(checkpoint_dir=bench_checkpoint_dir(), device=dev)
     tr.model.train()  # dropout 0.1 stays on, as in the reference
     steps_total = 5000  # stage-1 LR schedule (warmup 1000, hold 1666, cosine)
     STEP0 = 1000  # a chunk's steps are stage steps STEP0 .. STEP0 + S - 1
@@ -1248,9 +1373,18 @@ def setup_e2e(args, dev, rank, world, seed):
         extra.append(mel_variant_roofline(aug.augment_device(src, lens), mplan, n))
         return extra
 
+    def outputs():
+        """The embedding pool the last timed step featurized (pipelined: chunk s + 1's, NaN rows
+        replaced; the same bits from run to run), and train_probe on it with the step's batch
+        rows and schedule, on the train stream."""
+        emb = pool if args.overlap == "off" else pools[count[0] % nbuf]
+        out = {"embeddings": emb}
+        out.update(train_probe(dev, seed, idx, y, sched, emb, neg, stream=None if args.overlap == "off" else ts))
+        return out
+
     return {
         "step": step, "staged_step": staged_step, "stages": stages, "roofline": roofline, "rooflines": rooflines,
-        "extra_rooflines": extra_rooflines,
+        "extra_rooflines": extra_rooflines, "outputs": outputs,
         "cpu_baseline": cpu_baseline, "units_per_step": n, "scaling": "weak", "unit": "clips/s",
         "metric": "audio clips/sec featurized+trained, 1.5 s @16 kHz, 1/2/4/8 GPU",
         "data": "synthetic TTS-like utterances (seeded, 0.3-1.5 s), synthetic noise + IR banks, synthetic "
@@ -1286,7 +1420,7 @@ def setup_e2e(args, dev, rank, world, seed):
                                    + ("all CUs" if eval_stream[0] is not None and not isinstance(
                                        eval_stream[0], torch.cuda.ExternalStream) else "a CU-masked set")
                                    if eval_stream[0] is not None else "")
-                                + f"; per-stage ms from {args.stage_steps} sequential steps")},
+                                + (f"; per-stage ms from {args.stage_steps} sequential steps" if args.full else ""))},
     }
 
 

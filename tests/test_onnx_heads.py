@@ -34,7 +34,7 @@ def test_fixture_pins_the_oracle_forward():
         assert 0.0 <= float(gold[f"zeros/{name}"][0]) <= 1.0
 
 
-@pytest.mark.skipif(not os.path.isdir(MODELS), reason="reference ONNX heads only in the build container")
+@pytest.mark.skipif(not os.path.isdir(MODELS), reason="the reference's shipped ONNX heads are not present")
 def test_reader_on_shipped_heads(tmp_path):
     from heybuddy.util.onnx_util import read_initializers, read_nodes
     from heybuddy.wakeword import WakeWordMLPModel

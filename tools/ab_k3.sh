@@ -13,7 +13,7 @@ for V in narrow wide; do
   for P in fetch write; do
     case $P in fetch) CTR=FETCH_SIZE ;; write) CTR=WRITE_SIZE ;; esac
     rm -rf $OUT/k3_${V}_$P
-    env $E timeout -k 10 300 rocprofv3 --pmc $CTR -f csv -d $OUT/k3_${V}_$P -o run -- python3 bench.py --steps 1 --warmup 1 --stage-steps 1 --no-cpu --no-check > $OUT/k3_${V}_$P.log 2>&1 || { tail -5 $OUT/k3_${V}_$P.log; exit 1; }
+    env $E timeout -k 10 300 rocprofv3 --pmc $CTR -f csv -d $OUT/k3_${V}_$P -o run -- python3 bench.py --full --steps 1 --warmup 1 --stage-steps 1 --no-cpu --no-check > $OUT/k3_${V}_$P.log 2>&1 || { tail -5 $OUT/k3_${V}_$P.log; exit 1; }
   done
   python3 tools/prof_summary.py --fetch $OUT/k3_${V}_fetch --write $OUT/k3_${V}_write --steps 1 --stage-steps 1 --config 5 --label "k3 $V" --out $OUT/k3_${V}_pmc.json > /dev/null
   python3 - $OUT/k3_${V}_pmc.json <<'PY'

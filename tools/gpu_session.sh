@@ -19,12 +19,12 @@ for S in ${STEPS:-tests bench cus}; do
       tail -1 $OUT/${TAG}_smoke.log ;;
     bench)
       echo "=== bench (driver settings) ${BENCH_ARGS:-}"
-      timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 ${BENCH_ARGS:-} > $OUT/${TAG}_bench_c5.json 2> $OUT/${TAG}_bench_c5.err || { tail -30 $OUT/${TAG}_bench_c5.err; exit 1; }
+      timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full ${BENCH_ARGS:-} > $OUT/${TAG}_bench_c5.json 2> $OUT/${TAG}_bench_c5.err || { tail -30 $OUT/${TAG}_bench_c5.err; exit 1; }
       cut -c1-400 $OUT/${TAG}_bench_c5.json ;;
     configs)
       for C in 1 2 3 4; do
         echo "=== bench config $C"
-        timeout -k 10 600 python bench.py --config $C > $OUT/${TAG}_bench_c$C.json 2> $OUT/${TAG}_bench_c$C.err || { tail -30 $OUT/${TAG}_bench_c$C.err; exit 1; }
+        timeout -k 10 600 python bench.py --config $C --full > $OUT/${TAG}_bench_c$C.json 2> $OUT/${TAG}_bench_c$C.err || { tail -30 $OUT/${TAG}_bench_c$C.err; exit 1; }
         cut -c1-300 $OUT/${TAG}_bench_c$C.json
       done ;;
     prof234)
