@@ -1594,6 +1594,11 @@ __global__ void __launch_bounds__(64) eq_kernel(EqArgs a) {
 //    v_permlane16/32_swap) leaves frame u of the wave's 64 bins on octet u. No
 //    LDS in the per-frame path; per kPvGroup frames one float per lane goes to
 //    LDS for the istft samples.
+//  * only the non-silent span: a clip placed into the window is mostly exact zeros, and a frame of 250
+//    zeros is 0 up to the overlap-added sample. The workgroup scans its rows once for the first / last
+//    non-zero sample and runs the groups from the first whose source frames can be non-zero to 36
+//    frames past the last (HBK_PS_SPAN=0: every frame); the resamplers read zeros outside the clip's
+//    own range of y samples (PitchArgs::yr), and a workgroup wholly outside it only stores zeros.
 // ps_resample_kernel (frame group, clip): polyphase sinc, taps in registers.
 constexpr int kPsFft = 250, kPsHop = 7, kPsBins = kPsFft / 2 + 1, kPsPad = kPsFft / 2;
 constexpr int kPsTapMax = HBK_PITCH_SHIFT_MAX_TAPS;    // 2 width + orig (142 / 139 at 16 kHz)
@@ -1635,8 +1640,10 @@ struct PitchArgs {
   int64_t out_stride;
   int L, f_in, f_out, l1, orig, nw, width, target;
   double rate;
-  float* y;       // [n][l1]: istft output (resampler input)
+  float* y;       // [n][l1]: istft output (resampler input), written over the frames the vocoder ran
   float* taps;    // [nw][kPsTapMax]
+  int2* yr;       // [n]: the y samples [x, y) of the clip's own span (all written); y is zero outside, unread
+  int span;       // 1: the vocoder runs over the workgroup's non-silent span only (0: every frame)
 };
 
 __device__ __forceinline__ int ps_i0(const PitchArgs& a, int t, float& alpha) {
@@ -1652,6 +1659,7 @@ struct PvClip {
   float xs[256];              // xp[0, 250) (frame 0's direct DFT)
   float gh[2][kPvGh][8];      // G(t, s) over wave w's 64 bins, row t mod kPvGh (s = 7: unused)
   int cnt0;
+  int lo, hi;                 // first / last non-zero sample of the clip (lo > hi: all zero)
 };
 struct PvShared {
   cf tw[256];                 // e^{+2 pi i q / 250}
@@ -1751,6 +1759,45 @@ __device__ __forceinline__ void pv_load_rows(const PitchArgs& a, PvShared& sh, c
   }
 }
 
+// first / last sample of the clip row with v != 0.f (the predicate of the frames' non-zero count: NaN is
+// non-zero, -0 is zero), merged into the workgroup's span. One read of the row, 8 loads in flight per lane.
+__device__ __forceinline__ void pv_scan_span(PvClip& C, const float* xr, int L, int lane) {
+  int lo = INT_MAX, hi = -1;
+  int done = 0;  // samples covered by the aligned part
+  if ((reinterpret_cast<uintptr_t>(xr) & 15) == 0) {
+    const float4* x4 = reinterpret_cast<const float4*>(xr);
+    const int n4 = L >> 2;
+    for (int q0 = 0; q0 < n4; q0 += 128 * 8) {
+      float4 v[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int q = q0 + 128 * j + lane;
+        v[j] = q < n4 ? x4[q] : float4{0.f, 0.f, 0.f, 0.f};
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int p = 4 * (q0 + 128 * j + lane);
+        const bool b0 = v[j].x != 0.f, b1 = v[j].y != 0.f, b2 = v[j].z != 0.f, b3 = v[j].w != 0.f;
+        if (b0 || b1 || b2 || b3) {
+          lo = min(lo, p + (b0 ? 0 : b1 ? 1 : b2 ? 2 : 3));
+          hi = max(hi, p + (b3 ? 3 : b2 ? 2 : b1 ? 1 : 0));
+        }
+      }
+    }
+    done = 4 * n4;
+  }
+  for (int p = done + lane; p < L; p += 128) {
+    if (xr[p] != 0.f) {
+      lo = min(lo, p);
+      hi = max(hi, p);
+    }
+  }
+  if (hi >= 0) {
+    atomicMin(&C.lo, lo);
+    atomicMax(&C.hi, hi);
+  }
+}
+
 #ifdef HBK_PHASE_TIMING
 // profiling build: wave 0 of each block sums the s_memtime cycles of the
 // vocoder's phases locally, adds them to g_aug_phase[16 + i] at the end
@@ -1793,7 +1840,12 @@ ps_vocoder_kernel(PitchArgs a) {
     sh.tw64[q][1] = -sn;
   }
   if (lane == 0) C.cnt0 = 0;
+  if (lane == 0) {
+    C.lo = INT_MAX;
+    C.hi = -1;
+  }
   __syncthreads();
+  if (a.span) pv_scan_span(C, xr, a.L, lane);
   int nz = 0;
   for (int q = lane; q < kPsFft; q += 128) {
     const float v = ps_xp(xr, a.L, q);
@@ -1841,15 +1893,14 @@ ps_vocoder_kernel(PitchArgs a) {
       q -= q >= kPsFft ? kPsFft : 0;
     }
   };
-  pv_t xre, xim;
-  {
+  pv_t xre = pv_t(0), xim = pv_t(0);
+  int cnt = __builtin_amdgcn_readfirstlane(C.cnt0);
+  if (cnt != 0) {  // (a clip's count is wave-uniform; an all-zero frame is 0 without the 250-term sum)
     double dre, dim;
     direct(dre, dim);
     xre = static_cast<pv_t>(dre);
     xim = static_cast<pv_t>(dim);
   }
-  int cnt = __builtin_amdgcn_readfirstlane(C.cnt0);
-  if (cnt == 0) xre = xim = pv_t(0);
   int sf = 0;  // last slid frame
   int anchor = 0;  // frame of the last direct DFT
   static_assert(sizeof(sh.wt[0]) == 128 * sizeof(float4), "wt rows of 128 lanes");
@@ -1903,11 +1954,17 @@ ps_vocoder_kernel(PitchArgs a) {
   cf ca, na, pa;
   float cm, nm, pm;
   polar(ca, cm);
+  // the non-zero counts of frames c, c + 1 (cnt: frame sf), and the last frame of the last group in which
+  // an output frame had a source frame with a non-zero sample (wave-uniform): an istft sample none of whose
+  // 36 frames' groups had one is exactly 0, as in the FFT path (else G(t, r) - G(t - 36, r + 2), two
+  // roundings of one value, leaves a residue)
+  int cntc = cnt, cntn, lastnz = INT_MIN / 2;
   {
     pv_t nre, nim;
     int ncnt;
     slide_to(nre, nim, ncnt, C.d[sf + 1 - fb]);
     commit(nre, nim, ncnt);
+    cntn = cnt;
     polar(na, nm);
     slide_to(nre, nim, ncnt, C.d[sf + 1 - fb]);
     commit(nre, nim, ncnt);
@@ -1928,9 +1985,79 @@ ps_vocoder_kernel(PitchArgs a) {
   const cf e7 = sh.tw[q7];
   const int jmax = (a.l1 + kPsPad - 1) / kPsHop;  // the frame of the last istft sample
   float* y = a.y + static_cast<int64_t>(e) * a.l1;
-  HBK_PVT(0);  // init: tables, frame 0, the first rows
+  // The groups to run: [t_beg, t_last], over the union of the workgroup's clips' non-silent spans
+  // (workgroup-uniform: the loop holds barriers). A frame whose 250 samples are zero has X = 0, so
+  //  * before the first non-zero sample every output frame adds Z = 0: at the first group whose source
+  //    frames (up to c + 2) can be non-zero the state is exactly X = 0, cnt = 0, u = (1, 0), |X| = 0,
+  //    R = (1, 0), Q = 0, G = 0, and the loop starts there with the integer state of the full loop;
+  //  * after the last output frame with a non-zero source frame Q is constant, and 36 frames on
+  //    G(t, r) - G(t - 36, r + 2) is zero: the loop ends there, and the resampler reads zeros.
+  // A span that comes within 250 samples of either end reaches into the reflect padding: no skip there.
+  // frames_of: the output frames [tb, tl] of a span of samples [lo, hi] (lo > hi: none), tb a group's first
+  auto frames_of = [&](int lo, int hi, int& tb, int& tl) {
+    tb = 0;
+    tl = jmax;
+    float al;
+    if (lo > hi) {
+      tl = -1;  // silent: no frames, y is zero everywhere
+      return;
+    }
+    if (lo > 2 * kPsPad && a.rate < 2.0) {  // (rate < 2: c steps by at most 2 per frame, c = i0(t) after frame t)
+      const int fz = (lo - kPsPad) / kPsHop - 1;  // source frames <= fz are all zero (7 f + 124 < lo)
+      int tg = min(static_cast<int>((fz - 2) / a.rate), a.f_out - 1) & ~(kPvGroup - 1);
+      while (tg > 0 && ps_i0(a, tg - 1, al) + 2 > fz) tg -= kPvGroup;  // sf = c + 2 <= fz at the group's top
+      tb = max(tg, 0);
+    }
+    if (hi < a.L - 1 - 2 * kPsPad) {
+      const int fn = min((hi + kPsPad) / kPsHop, a.f_in - 1);  // the last source frame that can be non-zero
+      int t = max(min(a.f_out - 1, static_cast<int>((fn + 1) / a.rate) + 1), 0);
+      while (t > 0 && ps_i0(a, t, al) > fn) --t;  // the last output frame with i0 <= fn
+      while (t + 1 < a.f_out && ps_i0(a, t + 1, al) <= fn) ++t;
+      tl = min(jmax, t + 36);
+    }
+  };
+  int t_beg = 0, t_last = jmax;
+  {
+    // the clip's own frames give the y range its resampler reads (the rest of y is zero, whatever a
+    // partner's longer span made this workgroup compute there)
+    int tb = 0, tl = jmax;
+    if (a.span) {
+      int lo = INT_MAX, hi = -1;
+      for (int i = 0; i < kPvClips; ++i) {
+        lo = min(lo, sh.c[i].lo);
+        hi = max(hi, sh.c[i].hi);
+      }
+      frames_of(lo, hi, t_beg, t_last);
+      frames_of(C.lo, C.hi, tb, tl);
+    }
+    if (lane == 0 && live)
+      a.yr[e] = tl < tb ? int2{0, 0}
+                        : int2{max(kPsHop * tb - kPsPad, 0), min(kPsHop * (tl + 1) - kPsPad, a.l1)};
+  }
+  if (t_beg > 0) {
+    // the full loop's restart frames up to t_beg (sf = c + 2 = i0(t0 - 1) + 2 at the top of group t0)
+    for (int t0 = kPvGroup; t0 < t_beg; t0 += kPvGroup) {
+      float al;
+      const int s = ps_i0(a, t0 - 1, al) + 2;
+      if (s - anchor >= kPvRestart && s < a.f_in) anchor = s;
+    }
+    float al;
+    c = ps_i0(a, t_beg - 1, al);
+    sf = c + 2;
+    xre = xim = pv_t(0);
+    cnt = cntc = cntn = 0;
+    ca = na = pa = cf{1.f, 0.f};
+    cm = nm = pm = 0.f;
+    qz = ((t_beg % kPsFft) * dq) % kPsFft;
+    __syncthreads();  // the prologue's reads of the d rows
+    for (int q = lane; q < 2 * kPvGh * 8; q += 128) (&C.gh[0][0][0])[q] = 0.f;  // G(t, .) = 0 for t < t_beg
+    fb = sf + 1;
+    pv_load_rows(a, sh, xr, cl, lane, fb);
+    __syncthreads();
+  }
+  HBK_PVT(0);  // init: the span, tables, frame 0, the first rows
 
-  for (int t0 = 0; t0 <= jmax; t0 += kPvGroup) {
+  for (int t0 = t_beg; t0 <= t_last; t0 += kPvGroup) {
     // the group's source frames (and one ahead) must be resident: refill the d rows
     {
       float al;
@@ -1947,17 +2074,20 @@ ps_vocoder_kernel(PitchArgs a) {
       __syncthreads();
       for (int q = lane; q < kPsFft; q += 128) C.xs[q] = ps_xp(xr, a.L, kPsHop * sf + q);
       __syncthreads();
-      double dre, dim;
-      direct(dre, dim);
-      xre = static_cast<pv_t>(dre);
-      xim = static_cast<pv_t>(dim);
-      if (cnt == 0) xre = xim = pv_t(0);
+      xre = xim = pv_t(0);
+      if (cnt != 0) {
+        double dre, dim;
+        direct(dre, dim);
+        xre = static_cast<pv_t>(dre);
+        xim = static_cast<pv_t>(dim);
+      }
       anchor = sf;
     }
     HBK_PVT(1);  // row refills, restarts
     R *= __builtin_amdgcn_rsqf(fmaf(R.x, R.x, R.y * R.y));
     cf tz = sh.tw[qz];  // tw[qz]; i tw[qz] = (-y, x) is read through the packed ops' neg / op_sel modifiers
     const float* dg = C.d[0] + 8 * (sf + 1 - fb);  // FULL groups: frame u slides to row sf + 1 + u
+    int gor = 0;  // != 0: a frame of the group had a source frame with a non-zero sample
     float gr[kPvGroup];  // frame u: G(t0 + u, pv_g(lane & 7)) over the lane's octet
     float al_lane = 0.f;  // the source frame i0 and alpha of frame t0 + (lane & 7), read by frame u as lane u
     int i0_lane = 0;
@@ -1986,6 +2116,8 @@ ps_vocoder_kernel(PitchArgs a) {
         }
         if (!FULL && i0 > c + 1) {  // rate > 1: a second source frame this step (rare)
           ++c;
+          cntc = cntn;
+          cntn = cnt;
           ca = na;
           cm = nm;
           na = pa;
@@ -2002,6 +2134,9 @@ ps_vocoder_kernel(PitchArgs a) {
         const bool step = FULL || i0 > c;
         if (!FULL && !step && t > 0) R = cmul(R, cmul_conj(na, ca));  // the source frame repeats (uniform)
         c += step ? 1 : 0;
+        cntc = step ? cntn : cntc;
+        cntn = step ? cnt : cntn;
+        gor |= cntc | cntn;
         ca = step ? na : ca;
         cm = step ? nm : cm;
         na = step ? pa : na;
@@ -2095,9 +2230,11 @@ ps_vocoder_kernel(PitchArgs a) {
         const int lo = max(0, t - 35 + (r >= 5 ? 1 : 0)), hi = min(a.f_out - 1, t);
         // / (250 env) as a product with v_rcp_f32 (1 ulp; the IEEE division's scale / fixup
         // sequence is ~10 VALU per sample)
-        y[m] = (g1 - g2) * __builtin_amdgcn_rcpf(static_cast<float>(kPsFft) * static_cast<float>(hi - lo + 1));
+        const float v = (g1 - g2) * __builtin_amdgcn_rcpf(static_cast<float>(kPsFft) * static_cast<float>(hi - lo + 1));
+        y[m] = (gor == 0 && t - lastnz > 35) ? 0.f : v;
       }
     }
+    if (gor) lastnz = t0 + kPvGroup - 1;
     HBK_PVT(4);  // istft samples
   }
 #ifdef HBK_PHASE_TIMING
@@ -2124,6 +2261,18 @@ __global__ void ps_taps_kernel(PitchArgs a) {
   a.taps[i] = v;
 }
 
+// A resampler workgroup (clip e, frames [f0, f0 + frames), whose windows of kPsTapMax samples start at
+// y index j0) with no sample of the clip's computed y range [yr.x, yr.y) in its windows: every output
+// is zero. Stores them and returns true (workgroup-uniform), without reading y.
+__device__ __forceinline__ bool ps_window_silent(const PitchArgs& a, int2 yr, int e, int j0, int f0, int frames,
+                                                 int tid, int threads) {
+  if (j0 < yr.y && j0 + (frames - 1) * a.orig + kPsTapMax > yr.x) return false;
+  float* out = a.out + static_cast<int64_t>(a.idx[e]) * a.out_stride;
+  const int i1 = static_cast<int>(min(static_cast<int64_t>(f0 + frames) * a.nw, static_cast<int64_t>(a.L)));
+  for (int i = f0 * a.nw + tid; i < i1; i += threads) out[i] = 0.f;
+  return true;
+}
+
 __global__ void __launch_bounds__(128) ps_resample_kernel(PitchArgs a) {
   // frames in pairs (f, f + 1): ys2[p] interleaves their windows, (f q, f+1 q, f q+1, f+1 q+1) per
   // float4, so one packed FMA per tap serves both frames (the taps of a phase are the same)
@@ -2136,10 +2285,12 @@ __global__ void __launch_bounds__(128) ps_resample_kernel(PitchArgs a) {
   // y padded by (width, width + orig) zeros; frame f reads ypad[f orig + q]
   // (the window is read to kPsTapMax, past 2 width + orig, against zero taps)
   const int j0 = f0 * a.orig - a.width;
+  const int2 yr = a.yr[e];  // y is zero (and not written) outside [yr.x, yr.y)
+  if (ps_window_silent(a, yr, e, j0, f0, kPsResFrames, ph, 128)) return;
   for (int el = ph; el < kPsResFrames * kPsTapMax; el += 128) {
     const int fr = el / kPsTapMax, q = el - fr * kPsTapMax;  // q fastest: coalesced reads
     const int src = j0 + fr * a.orig + q;
-    ys2[fr >> 1][2 * q + (fr & 1)] = (src >= 0 && src < a.l1) ? y[src] : 0.f;
+    ys2[fr >> 1][2 * q + (fr & 1)] = (src >= yr.x && src < yr.y) ? y[src] : 0.f;
   }
   float tp[kPsTapMax];
   const float* tr = a.taps + min(ph, a.nw - 1) * kPsTapMax;
@@ -2192,6 +2343,8 @@ __global__ void __launch_bounds__(256) ps_resample_mfma_kernel(PitchArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int e = blockIdx.y, f0 = blockIdx.x * kRsFrames;
   const float* y = a.y + static_cast<int64_t>(e) * a.l1;
+  const int2 yr = a.yr[e];  // y is zero (and not written) outside [yr.x, yr.y)
+  if (ps_window_silent(a, yr, e, f0 * a.orig - a.width, f0, kRsFrames, tid, 256)) return;
   // staging: pair p = tid + 256 u of (frame p / 80, taps 2 (p % 80) and + 1)
   constexpr int kPairs = kRsFrames * kRsK / 2, kPer = kPairs / 256;
   float v0[kPer], v1[kPer];
@@ -2202,8 +2355,8 @@ __global__ void __launch_bounds__(256) ps_resample_mfma_kernel(PitchArgs a) {
     const int src = (f0 + fr) * a.orig - a.width + q;
     const int s0 = min(max(src, 0), a.l1 - 1), s1 = min(max(src + 1, 0), a.l1 - 1);
     const float x0 = y[s0], x1 = y[s1];
-    v0[u] = (src >= 0 && src < a.l1 && q < kPsTapMax) ? x0 : 0.f;
-    v1[u] = (src + 1 >= 0 && src + 1 < a.l1 && q + 1 < kPsTapMax) ? x1 : 0.f;
+    v0[u] = (src >= yr.x && src < yr.y && q < kPsTapMax) ? x0 : 0.f;
+    v1[u] = (src + 1 >= yr.x && src + 1 < yr.y && q + 1 < kPsTapMax) ? x1 : 0.f;
     mx = fmaxf(mx, fmaxf(fabsf(v0[u]), fabsf(v1[u])));
   }
   // B fragments: phases 16 (2 wave + t) + (lane & 15), taps 32 ks + 8 (lane >> 4) ..
@@ -2742,13 +2895,14 @@ static int64_t ps_bytes(const hbk::PitchArgs& a, int64_t n, int64_t* off) {
   auto up = [](int64_t b) { return (b + 255) & ~int64_t(255); };
   off[0] = off[1] = off[2] = off[3] = 0;           // y
   off[4] = up(n * a.l1 * 4);                       // taps
-  return off[4] + up(int64_t(kPsPhaseMax) * kPsTapMax * 4);
+  off[5] = off[4] + up(int64_t(kPsPhaseMax) * kPsTapMax * 4);  // the clips' computed y ranges
+  return off[5] + up(n * int64_t(sizeof(int2)));
 }
 
 int64_t hbk_pitch_shift_workspace_size(int64_t n, int64_t T, int32_t sample_rate, int32_t num, int32_t den) {
   hbk::PitchArgs a{};
   if (n <= 0 || ps_geometry(T, sample_rate, num, den, a) != HBK_OK) return 0;
-  int64_t off[5];
+  int64_t off[6];
   return ps_bytes(a, n, off);
 }
 
@@ -2764,7 +2918,7 @@ int hbk_pitch_shift(const float* x, int64_t x_stride, int64_t n, const int32_t* 
   const int rc = ps_geometry(T, sample_rate, num, den, a);
   if (rc != HBK_OK) return rc;
   if (x_stride < T || out_stride < T) return arg_error("stride < T");
-  int64_t off[5];
+  int64_t off[6];
   if (workspace_bytes < ps_bytes(a, n, off)) return arg_error("workspace too small (hbk_pitch_shift_workspace_size)");
   unsigned char* w = static_cast<unsigned char*>(workspace);
   a.x = x;
@@ -2775,6 +2929,12 @@ int hbk_pitch_shift(const float* x, int64_t x_stride, int64_t n, const int32_t* 
   a.n = static_cast<int>(n);
   a.y = reinterpret_cast<float*>(w + off[3]);
   a.taps = reinterpret_cast<float*>(w + off[4]);
+  a.yr = reinterpret_cast<int2*>(w + off[5]);
+  static const bool span_off = [] {  // HBK_PS_SPAN=0: every frame of every clip, the full resampler (A/B)
+    const char* s = getenv("HBK_PS_SPAN");
+    return s && s[0] == '0';
+  }();
+  a.span = span_off ? 0 : 1;
   hipStream_t st = as_stream(stream);
   hipLaunchKernelGGL(ps_taps_kernel, dim3(unsigned((a.nw * kPsTapMax + 255) / 256)), dim3(256), 0, st, a);
   HBK_LAUNCH_CHECK("ps_taps_kernel");

@@ -199,7 +199,7 @@ def load_to_device(path: str, device, dtype=None, chunk_rows: int = 65536, rows:
     stage = torch.empty((n, *mm.shape[1:]), dtype=src_dtype, device=device)
     for r0 in range(0, mm.shape[0], n):
         k = min(n, mm.shape[0] - r0)
-        if torch.cuda.is_available():
+        if out.is_cuda:
             torch.cuda.current_stream(out.device).synchronize()  # the previous chunk left the pinned buffer
         pinned[:k].numpy()[...] = mm[r0:r0 + k]
         stage[:k].copy_(pinned[:k], non_blocking=True)
