@@ -3031,10 +3031,13 @@ FusedWs fused_layout(int64_t B, int NG, int64_t n_params = 0) {
   w.hg_part = take(int64_t(24) * B * kH2);
   w.xhat[0] = take(Bp * kD);
   w.xhat[1] = take(Bp * kD);
-  w.U = take(int64_t(NG) * Bp * kH);
-  w.Xn = take(int64_t(NG) * Bp * kL);
-  w.dS = take(int64_t(NG) * Bp * kL);
-  w.dHG = take(int64_t(NG) * Bp * kH2);
+  // k3s reads these four unclamped, up to kK3sMaxR floats past an array's end (zeroed at use):
+  // each is followed by that many floats that nothing writes, whatever the order of the arrays
+  auto take_k3s = [&](int64_t n) { return take(n + kK3sMaxR); };
+  w.U = take_k3s(int64_t(NG) * Bp * kH);
+  w.Xn = take_k3s(int64_t(NG) * Bp * kL);
+  w.dS = take_k3s(int64_t(NG) * Bp * kL);
+  w.dHG = take_k3s(int64_t(NG) * Bp * kH2);
   w.rinfo[0] = take(Bp * 4);
   w.rinfo[1] = take(Bp * 4);
   w.mask[0] = take(Bp * kMaskW);
@@ -3225,6 +3228,8 @@ bool mlp_fused_supported(const hbk_mlp_plan& p) {
 int64_t mlp_fused_ws_floats(const hbk_mlp_plan& p, int64_t B) {
   return fused_layout(std::max<int64_t>(B, 1), static_cast<int>(p.g.size()), p.n_params).total;
 }
+
+int mlp_fused_step_variant(int64_t B, hipStream_t s) { return step_v2(B, s) ? 2 : 1; }
 
 // k1 + k2 (+ k3): the forward (inference) or forward/backward half of a step.
 #ifdef HBK_BOUNDS

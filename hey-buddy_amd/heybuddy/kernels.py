@@ -465,6 +465,14 @@ class MlpPlan:
             self._fused = bool(ok.value)
         return self._fused
 
+    def step_variant(self, batch: int, device) -> int:
+        """1 (k1a / k1b / k3) or 2 (k1s / k1c / k3s): the kernels step_fwd_bwd runs for
+        ``batch`` rows on ``device``'s current stream (hbk_mlp_step_variant)."""
+        v = ctypes.c_int32()
+        check(lib().hbk_mlp_step_variant(self._handle, int(batch), stream_ptr(torch.device(device)),
+                                         ctypes.byref(v)), "hbk_mlp_step_variant")
+        return v.value
+
     @staticmethod
     def new_state(device, adam_t: float = 0.0, salt: int = 0) -> torch.Tensor:
         """Device step state, both halves [0, 1, adam_t, 0, salt, 0, 0, 0]."""

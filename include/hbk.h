@@ -297,6 +297,9 @@ int hbk_mlp_gate_adam(const hbk_mlp_plan* plan, float* params, const float* buck
 #define HBK_STEP_WEIGHTS_READY 4
 #define HBK_STEP_DEFER_PARTIALS 8
 int hbk_mlp_fused_supported(const hbk_mlp_plan* plan, int32_t* supported);
+/* 1 = k1a/k1b/k3 (v1), 2 = k1s/k1c/k3s (v2): the variant hbk_mlp_step_fwd_bwd
+ * takes for `batch` rows on `stream`. Fused plans only. */
+int hbk_mlp_step_variant(const hbk_mlp_plan* plan, int64_t batch, void* stream, int32_t* variant);
 int hbk_mlp_step_fwd_bwd(const hbk_mlp_plan* plan, const float* params, const float* pool32, int64_t n32,
                          const void* pool16, int64_t n16, const int32_t* idx, int64_t idx_step_stride,
                          const float* y, int64_t y_step_stride, int64_t batch, const float* state,

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import step_oracle_cases as cases
 from oracle import golden_classifier as gc
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "classifier.npz")
@@ -103,20 +104,8 @@ def test_train_epoch_matches_reference(gold, inputs, tmp_path):
     out = tr.train_epoch(data, num_steps=24, warmup_steps=4, hold_steps=8, validation_steps=1000,
                          checkpoint_steps=100000)
     lr, nw, loss, hlr, rec, fp = [t.numpy() for t in out[:6]]
-    np.testing.assert_allclose(lr, gold["epoch/lr"], rtol=1e-6)
-    np.testing.assert_allclose(hlr, gold["epoch/hlr"], rtol=1e-6)
-    assert loss.shape == gold["epoch/loss"].shape
-    # the oracle's bounds (test_classifier_oracle.py): loss 2e-4; final
-    # parameters within 2e-4 except Adam's sign flips where a gradient sits at
-    # the fp32 noise floor (each flip moves a weight by up to 2 lr): at most
-    # 0.5 % of the 256,417 parameters, as in test_stages_gpu.py
-    np.testing.assert_allclose(loss, gold["epoch/loss"], rtol=2e-4, atol=1e-7)
-    np.testing.assert_allclose(rec, gold["epoch/recall"], atol=1e-6)
-    np.testing.assert_allclose(fp, gold["epoch/fp"], atol=1e-6)
     sd = tr.model.state_dict()
-    diffs = np.concatenate([np.abs(sd[k].cpu().numpy() - gold[f"epoch_final/{k}"]).ravel() for k in params])
-    assert (diffs > 2e-4).mean() <= 5e-3, (diffs > 2e-4).mean()
-    assert diffs.max() <= 5e-3, diffs.max()  # a flipped element: a few lr-sized steps at most
+    cases.check_epoch_against_gold(gold, params, lr, hlr, loss, rec, fp, {k: sd[k].cpu().numpy() for k in params})
     # checkpoint + resume round trip keeps the Adam state
     tr.save_checkpoint("t")
     tr2 = WakeWordTrainer(checkpoint_dir=str(tmp_path))
@@ -150,9 +139,10 @@ def test_graph_steps_equal_eager_steps(inputs, tmp_path, monkeypatch):
         torch.cuda.synchronize()
         runs.append((tr.model.flat_parameters.clone(), tr._m.clone(), tr._v.clone(), out[2].clone(),
                      len(getattr(tr, "_graphs", {}))))
+        lr_sum = float(out[0].sum())  # the schedule's: the same in both runs
     (p1, m1, v1, l1, ng), (p0, m0, v0, l0, _) = runs
     assert ng >= 1
     np.testing.assert_allclose(l1.numpy(), l0.numpy(), rtol=1e-4, atol=1e-6)
     d = (p1 - p0).abs()
-    assert float((d > 1e-5).float().mean()) < 1e-3 and float(d.max()) <= 2e-2
+    assert float((d > 1e-5).float().mean()) < 1e-3 and float(d.max()) <= min(2e-2, 2 * lr_sum)
     assert float(((m1 - m0).abs() > 1e-5 * m0.abs().max()).float().mean()) < 1e-3

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import step_oracle_cases as cases
 from oracle import golden_classifier as gc
 
 pytestmark = pytest.mark.gpu
@@ -50,16 +51,9 @@ def test_fused_grads_match_reference():
     m = _model(params)
     bucket, prob = _fused_grads(m, x, y)
     plan = m.plan
-    stats = bucket[plan.n_params:].cpu().numpy()
-    n_sel = int(gold["n_sel"])
-    assert int(stats[0]) == n_sel
-    np.testing.assert_allclose(stats[1] / n_sel, float(gold["loss"]), rtol=1e-5)
-    np.testing.assert_allclose(prob.cpu().numpy(), gold["prob"], rtol=1e-4, atol=1e-6)
-    g = plan.views(bucket[:plan.n_params] / n_sel)
-    for k in params:
-        ref = gold[f"grad/{k}"]
-        scale = np.abs(ref).max() + 1e-12
-        np.testing.assert_allclose(g[k].cpu().numpy() / scale, ref / scale, rtol=0, atol=1e-4, err_msg=k)
+    g = plan.views(bucket[:plan.n_params] / int(gold["n_sel"]))
+    cases.check_step_against_gold(gold, params, bucket[plan.n_params:].cpu().numpy(), prob.cpu().numpy(),
+                                  {k: g[k].cpu().numpy() for k in params})
 
 
 @pytest.mark.parametrize("B", [1100, 1000, 550, 500, 273, 100, 17, 1])
@@ -152,7 +146,7 @@ def test_train_indexed_equals_eager_steps(tmp_path):
     np.testing.assert_allclose(h1[:, [0, 2, 4, 5, 6, 7]].cpu().numpy(), h0[:, [0, 2, 4, 5, 6, 7]].cpu().numpy())
     np.testing.assert_allclose(h1[:, 3].cpu().numpy(), h0[:, 3].cpu().numpy(), rtol=1e-4)
     d = (p1 - p0).abs()
-    assert float((d > 1e-5).float().mean()) < 1e-3 and float(d.max()) <= 2e-2
+    assert float((d > 1e-5).float().mean()) < 1e-3 and float(d.max()) <= min(2e-2, 2 * float(lr.sum()))
     torch.testing.assert_close(s1, s0)
 
 
@@ -208,7 +202,7 @@ def test_train_indexed_split_with_eval_between_equals_one_call(tmp_path):
         np.testing.assert_allclose(h1[:, [0, 2, 4, 5, 6, 7]].cpu().numpy(), h0[:, [0, 2, 4, 5, 6, 7]].cpu().numpy())
         np.testing.assert_allclose(h1[:, 3].cpu().numpy(), h0[:, 3].cpu().numpy(), rtol=1e-4)
         d = (p1 - p0).abs()
-        assert float((d > 1e-5).float().mean()) < 1e-3 and float(d.max()) <= 2e-2
+        assert float((d > 1e-5).float().mean()) < 1e-3 and float(d.max()) <= min(2e-2, 2 * float(lr.sum()))
         torch.testing.assert_close(s1, s0)
 
 
@@ -294,7 +288,7 @@ def test_v2_step_on_the_train_partition_equals_v1(tmp_path):
     np.testing.assert_allclose(h1[:, [0, 2, 4, 5, 6, 7]].cpu().numpy(), h0[:, [0, 2, 4, 5, 6, 7]].cpu().numpy())
     np.testing.assert_allclose(h1[:, 3].cpu().numpy(), h0[:, 3].cpu().numpy(), rtol=1e-4)
     d = (p1 - p0).abs()
-    assert float((d > 1e-5).float().mean()) < 1e-3 and float(d.max()) <= 2e-2
+    assert float((d > 1e-5).float().mean()) < 1e-3 and float(d.max()) <= min(2e-2, 2 * float(sched[:, 0].sum()))
     torch.testing.assert_close(s1, s0)
 
 
@@ -349,4 +343,4 @@ def test_train_epoch_device_iterator_runs_indexed_and_equals_eager(tmp_path, mon
     for i in (6, 7, 8, 9, 10):  # validation fp/h, recall; testing accuracy, recall, fp rate
         np.testing.assert_allclose(hf[i].numpy(), he[i].numpy(), rtol=1e-5, atol=1e-5)
     d = (pf - pe).abs()
-    assert float((d > 1e-5).float().mean()) < 1e-3 and float(d.max()) <= 2e-2
+    assert float((d > 1e-5).float().mean()) < 1e-3 and float(d.max()) <= min(2e-2, 2 * float(he[0].sum()))

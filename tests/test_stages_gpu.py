@@ -19,9 +19,12 @@ import numpy as np
 import pytest
 import torch
 
+import step_oracle_cases as cases
 from oracle import golden_classifier as gc
 
 pytestmark = pytest.mark.gpu
+
+STAGE_HISTORIES = ("lr", "nw", "hlr", "vfp", "vrecall", "recall", "fp", "loss")
 
 
 class StageIterator:
@@ -57,23 +60,6 @@ def test_three_stage_training_matches_reference(tmp_path):
     testing = [(torch.from_numpy(x), torch.from_numpy(y)) for x, y in test]
     h = tr(it, validation=validation, testing=testing, num_steps=gc.STAGE_STEPS,
            validation_steps=gc.STAGE_VAL_STEPS, checkpoint_steps=100000, name="stages")
-    lens = list(gold["stage_lengths"])
-    assert lens == [8, 16, 32]
-    sizes, o = [], 0
-    for n in lens:  # one batch per stage is fetched past the last step, as in the reference
-        sizes += it.sizes[o:o + n]
-        o += n + 1
-    np.testing.assert_array_equal(sizes, gold["batch_sizes"])
-    np.testing.assert_allclose(h["lr"].numpy(), gold["hist/learning_rate"], rtol=1e-6)
-    np.testing.assert_allclose(h["nw"].numpy(), gold["hist/negative_weight"], rtol=1e-6)
-    np.testing.assert_allclose(h["hlr"].numpy(), gold["hist/high_loss_rate"], rtol=1e-6)
-    np.testing.assert_allclose(h["vfp"].numpy(), gold["hist/validation_false_positive_rate_per_hour"], rtol=1e-6)
-    np.testing.assert_allclose(h["vrecall"].numpy(), gold["hist/validation_recall"], atol=1e-6)
-    np.testing.assert_allclose(h["recall"].numpy(), gold["hist/recall"], atol=1e-6)
-    np.testing.assert_allclose(h["fp"].numpy(), gold["hist/false_positive_rate"], atol=1e-6)
-    np.testing.assert_allclose(h["loss"].numpy(), gold["hist/loss"], rtol=2e-4, atol=1e-7)
     sd = tr.model.state_dict()
-    d = np.concatenate([np.abs(sd[k].cpu().numpy() - gold[f"final/{k}"]).ravel() for k in params])
-    bound = 2 * float(np.sum(gold["hist/learning_rate"]))
-    assert float(np.mean(d <= 2e-4)) >= 0.995, float(np.mean(d <= 2e-4))
-    assert float(d.max()) <= bound, (float(d.max()), bound)
+    cases.check_stages_against_gold(gold, params, {k: h[k].numpy() for k in STAGE_HISTORIES}, it.sizes,
+                                    {k: sd[k].cpu().numpy() for k in params})
