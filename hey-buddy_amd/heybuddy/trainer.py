@@ -25,6 +25,7 @@ import contextlib
 import math
 import os
 import random
+import weakref
 from time import perf_counter
 from typing import Any, Dict, List, Optional, Tuple, Union
 
@@ -104,15 +105,25 @@ class Trainer(nn.Module):
         self._fstate = torch.tensor([0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0] * 2, dtype=torch.float32, device=dev)
         self._parity = 0
         self._bucket = torch.zeros(flat.numel() + self.model.plan.N_STATS, dtype=torch.float32, device=dev)
-        self._graphs = {}
+        self._seed_base_v: Optional[int] = None  # the fused path's dropout stream (_seed_base draws it once)
+        self._drop_derived_state()
+
+    def _drop_derived_state(self) -> None:
+        """All cached device state derived from the parameters' addresses, the device
+        or the caller's data, empty: whatever re-creates or moves the flat parameters
+        calls this, and every user rebuilds its slot on demand."""
+        self._graphs: Dict[tuple, tuple] = {}  # _captured: key -> (kept buffers, graphs, CU mask)
+        self._epoch_bufs: Dict[tuple, tuple] = {}  # _epoch_buffers: idx shape -> (idx, y, sched)
+        self._pool_cache = self._eval_cache = None  # _cat_pools' / _eval_from_iterators' (_live_key, ..., value)
+        # train_indexed's workspace, _graph_step's device [lr, neg_weight, seed], _history_buffer's step record
+        self._indexed_ws = self._scalars = self._history = None
 
     def _apply(self, fn, recurse=True):
         super()._apply(fn, recurse)
-        if hasattr(self, "_m"):
-            self._m, self._v = fn(self._m), fn(self._v)
-            self._state, self._ctrl, self._bucket = fn(self._state), fn(self._ctrl), fn(self._bucket)
-            self._fstate = fn(self._fstate)
-            self._graphs = {}
+        self._m, self._v = fn(self._m), fn(self._v)
+        self._state, self._ctrl, self._bucket = fn(self._state), fn(self._ctrl), fn(self._bucket)
+        self._fstate = fn(self._fstate)
+        self._drop_derived_state()
         return self
 
     @property
@@ -350,8 +361,21 @@ def _recall(tp: float, n_pos: float) -> float:
     return tp / n_pos if n_pos > 0 else 0.0
 
 
-def _device_pools(it: Any) -> Optional[List[Tuple[torch.Tensor, int, int]]]:
-    """[(rows [n, 1536] f32 / f16 on the device, per-batch count, label)] of a
+def _live_key(objs: List[Any], on_dead: Any = None) -> list:
+    """What a data cache remembers of its inputs without keeping them alive (the pools are
+    multi-GB tables): weak references, and a tensor's in-place version, shape and dtype."""
+    return [(weakref.ref(o, on_dead), (o._version, o.shape, o.dtype) if isinstance(o, torch.Tensor) else None)
+            for o in objs]
+
+
+def _same_live(key: list, objs: List[Any]) -> bool:
+    """``objs`` are the very objects of the key, alive (a dead reference gives None) and unwritten."""
+    return len(key) == len(objs) and all(r() is o and was == now
+                                         for (r, was), o, (_, now) in zip(key, objs, _live_key(objs)))
+
+
+def _device_pools(it: Any) -> Optional[List[Tuple[Any, int, int]]]:
+    """[(DevicePool of [n, 16, 96] f32 / f16 rows on the device, per-batch count, label)] of a
     device-pool TrainingDatasetIterator (positives first, as next_batch), or None."""
     from heybuddy.dataset.training import DevicePool, TrainingDatasetIterator
     if not isinstance(it, TrainingDatasetIterator):
@@ -375,9 +399,12 @@ class _IndexedEpoch:
     the rows and order of S next_batch() calls), labels, and the lr / negative-weight
     schedule on the device; the steps run as train_indexed segments (hipGraphs of 50
     steps, rows gathered on the device) up to each validation / checkpoint point, and
-    validation / testing iterators become one EvalPasses over their pools. Same rows,
-    same kernels and dropout stream as the per-batch loop (_step); HBK_TRAIN_EAGER=1 keeps
-    the per-batch loop."""
+    validation / testing iterators become one EvalPasses over their pools. Same kernels
+    and dropout stream as the per-batch loop (_step; HBK_TRAIN_EAGER=1 keeps it). Same
+    rows only while no pool wraps within the stage and in the first stage of a call:
+    the pools share the iterator's generator, so the bulk take_indices reorders the
+    randperm draws once a pool wraps, and the eager loop's ``enumerate ... break``
+    consumes one extra batch per stage."""
 
     @classmethod
     def make(cls, tr: "WakeWordTrainer", training: Any, validation: Any, testing: Any, num_steps: int,
@@ -387,15 +414,13 @@ class _IndexedEpoch:
         dsets = _device_pools(training)
         if dsets is None:
             return None
-        if validation is not None and not isinstance(validation, EvalPasses):
-            vd = _device_pools(validation)
-            if vd is None or {lab for _, _, lab in vd} != {0, 1} or validation.max_samples is None:
-                return None
-        if testing is not None:
-            td = _device_pools(testing)
-            if (td is None or {lab for _, _, lab in td} != {0, 1} or testing.max_samples is None
-                    or validation is None or isinstance(validation, EvalPasses)):
-                return None
+        if testing is not None and (validation is None or isinstance(validation, EvalPasses)):
+            return None
+        for it in (validation, testing):  # both labels and a pass length: what _eval_from_iterators needs
+            if it is not None and not isinstance(it, EvalPasses):
+                ps = _device_pools(it)
+                if ps is None or {lab for _, _, lab in ps} != {0, 1} or it.max_samples is None:
+                    return None
         return cls(tr, training, dsets, validation, testing, num_steps, threshold, act_thr, history)
 
     def __init__(self, tr, training, dsets, validation, testing, num_steps, threshold, act_thr, history):
@@ -403,7 +428,7 @@ class _IndexedEpoch:
         dev = tr.device
         mx = training.max_samples
         self.S = num_steps if mx is None else min(num_steps, int(mx))
-        p32, p16, off = tr._cat_pools([d.data for d, _, _ in dsets])
+        self.p32, self.p16, off = tr._cat_pools([d.data for d, _, _ in dsets])
         cols, ys = [], []
         for d, n, lab in dsets:  # the S batches' rows, dataset by dataset (next_batch's column order)
             ix = d.take_indices(n * self.S).view(self.S, n).to(torch.int64) + off[id(d.data)]
@@ -415,24 +440,11 @@ class _IndexedEpoch:
         rank, world = tr._world()
         if world > 1:  # distributed.shard_batch's class-stratified slice
             idx, y = idx[:, rank::world], y[rank::world]
-        # the stage's index / label / schedule buffers persist per shape on the trainer, so the
-        # next epoch's (and the next __call__'s) segments replay the hipGraphs captured now: the
-        # graphs bake in these addresses, and a capture per stage per call cost ~20 ms of the
-        # 3-stage bench run (bench.py's cli_path)
         idx = idx.to(torch.int32).contiguous()
-        key = (tuple(idx.shape), str(dev))
-        cache = getattr(tr, "_epoch_bufs", None)
-        if cache is None:
-            cache = tr._epoch_bufs = {}
-        bufs = cache.get(key)
-        if bufs is None:
-            bufs = cache[key] = (torch.empty_like(idx), torch.empty_like(y),
-                                          torch.zeros((max(self.S, 1), 2), dtype=torch.float32, device=dev))
-        self.idx, self.y, self.sched = bufs
+        self.idx, self.y, self.sched = tr._epoch_buffers(idx, y)
         self.idx.copy_(idx)
         self.y.copy_(y)
         self.sched.zero_()
-        self.p32, self.p16 = p32, p16
         self.done = 0
         self.validation = validation
         if validation is not None and not isinstance(validation, EvalPasses):
@@ -529,34 +541,51 @@ class WakeWordTrainer(Trainer):
     def _seed_base(self) -> int:
         """Dropout stream of the fused path: fixed per trainer; every step adds
         its index and every epoch its salt (state[4]) on the device."""
-        if not hasattr(self, "_seed_base_v"):
+        if self._seed_base_v is None:
             self._seed_base_v = random.getrandbits(40)
         return self._seed_base_v
+
+    def _captured(self, key: tuple, make: Any, masked: bool = False) -> Tuple[Any, List["torch.cuda.CUDAGraph"]]:
+        """(kept buffers, graphs) of ``key``, captured on a miss: ``make()`` allocates the buffers the
+        graphs own and returns (kept, [callables]); each callable becomes one graph, captured on a
+        side stream (``masked``: with the replay stream's CU mask, capture_stream). The entry keeps
+        ``kept`` alive and never holds the pools. Keys are addresses (data_ptr) and scalars on purpose: a
+        graph replays into addresses, so a tensor on the same address with the same shape is a correct hit."""
+        entry = self._graphs.get(key)
+        if entry is None:
+            self._evict_graphs()
+            kept, fns = make()
+            dev = self.device
+            side, mask = capture_stream(dev) if masked else (torch.cuda.Stream(dev), None)
+            side.wait_stream(torch.cuda.current_stream(dev))
+            graphs = [torch.cuda.CUDAGraph() for _ in fns]
+            for gr, fn in zip(graphs, fns):
+                with torch.cuda.graph(gr, stream=side):
+                    fn()
+            torch.cuda.current_stream(dev).wait_stream(side)
+            entry = self._graphs[key] = (kept, graphs, mask)
+        return entry[0], entry[1]
 
     def _fused_graph_step(self, x: torch.Tensor, y: torch.Tensor, lr: float, neg_weight: float,
                           threshold: float, activation_threshold: float, history: Optional[torch.Tensor],
                           p: float, world: int) -> None:
-        """One fused step as captured hipGraphs, one set per (batch size, parity,
-        thresholds, dropout p, history buffer). Each graph owns its staging rows,
-        its (lr, neg_weight) cell and its workspace, so no later allocation can
-        move memory a graph replays into. world == 1: one graph per step;
-        data-parallel: forward/backward graph, all-reduce, update graph."""
+        """One fused step as captured hipGraphs, one set per (batch size, parity, thresholds,
+        dropout p, history buffer), which owns its staging rows, (lr, neg_weight) cell and
+        workspace: no later allocation can move memory a graph replays into. One graph per step
+        where the all-reduce is capturable, else forward/backward graph, all-reduce, update graph."""
         dev = self.device
         plan = self.model.plan
         flat = self.model.flat_parameters
         B = int(x.shape[0])
         key = (B, self._parity, float(threshold), float(activation_threshold), float(p), world,
                None if history is None else (history.data_ptr(), history.shape[0]), self._state_ptrs())
-        g = self._graphs.get(key)
-        if g is None:
-            self._evict_graphs()
+        parity = self._parity
+
+        def make():
             sx = torch.zeros((B, plan.d_in), dtype=torch.float32, device=dev)
             sy = torch.zeros(B, dtype=torch.float32, device=dev)
             sched = torch.zeros((1, 2), dtype=torch.float32, device=dev)
             ws = torch.empty(plan.workspace_bytes(B), dtype=torch.uint8, device=dev)
-            side = torch.cuda.Stream(dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            parity = self._parity
 
             def fwd():
                 plan.step_fwd_bwd(flat, self._bucket, self._fstate, parity, sy, B, pool32=sx, sched=sched,
@@ -567,33 +596,22 @@ class WakeWordTrainer(Trainer):
                 plan.step_update(flat, self._bucket, self._m, self._v, self._fstate, parity, sched=sched,
                                  beta1=BETAS[0], beta2=BETAS[1], eps=EPS, history=history)
 
-            graphs = []
-            with torch.cuda.stream(side):
-                if distributed.graph_capturable(world):  # one graph per step, the RCCL all-reduce inside
-                    gr = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(gr, stream=side):
-                        fwd()
-                        distributed.reduce_bucket(self._bucket)
-                        upd()
-                    graphs.append(gr)
-                else:
-                    for fn in (fwd, upd):
-                        gr = torch.cuda.CUDAGraph()
-                        with torch.cuda.graph(gr, stream=side):
-                            fn()
-                        graphs.append(gr)
-            torch.cuda.current_stream(dev).wait_stream(side)
-            g = self._graphs[key] = {"x": sx, "y": sy, "sched": sched, "ws": ws, "graphs": graphs}
-        g["x"].copy_(x.reshape(B, -1), non_blocking=True)
-        g["y"].copy_(y, non_blocking=True)
-        g["sched"][0, 0].fill_(float(lr))
-        g["sched"][0, 1].fill_(float(neg_weight))
-        if len(g["graphs"]) == 1:
-            g["graphs"][0].replay()
-        else:
-            g["graphs"][0].replay()
+            def whole():  # one graph per step, the RCCL all-reduce inside
+                fwd()
+                distributed.reduce_bucket(self._bucket)
+                upd()
+
+            return (sx, sy, sched, ws), [whole] if distributed.graph_capturable(world) else [fwd, upd]
+
+        (sx, sy, sched, _), graphs = self._captured(key, make)
+        sx.copy_(x.reshape(B, -1), non_blocking=True)
+        sy.copy_(y, non_blocking=True)
+        sched[0, 0].fill_(float(lr))
+        sched[0, 1].fill_(float(neg_weight))
+        graphs[0].replay()
+        if len(graphs) > 1:
             distributed.reduce_bucket(self._bucket)
-            g["graphs"][1].replay()
+            graphs[1].replay()
 
     def train_indexed(self, idx: torch.Tensor, y: torch.Tensor, sched: torch.Tensor,
                       pool32: Optional[torch.Tensor] = None, pool16: Optional[torch.Tensor] = None,
@@ -627,9 +645,8 @@ class WakeWordTrainer(Trainer):
         p32 = None if pool32 is None else pool32.reshape(pool32.shape[0], -1)
         p16 = None if pool16 is None else pool16.reshape(pool16.shape[0], -1)
         _, world = self._world()
-        ws = self._indexed_ws = getattr(self, "_indexed_ws", None)
-        need = plan.workspace_bytes(B)
-        if ws is None or ws.numel() < need or ws.device != dev:
+        ws, need = self._indexed_ws, plan.workspace_bytes(B)
+        if ws is None or ws.numel() < need:
             ws = self._indexed_ws = torch.empty(need, dtype=torch.uint8, device=dev)
             continued = False  # a new workspace holds no prefetched rows or weight cache
 
@@ -637,7 +654,6 @@ class WakeWordTrainer(Trainer):
         # launches (prefetch_next); only the first step of this call gathers its own.
         # One process: the weight-gradient slabs go straight to the update (no all-reduce between).
         defer = not distributed.reduces()
-
         # HBK_NO_PREFETCH=1 (A/B): every step gathers its own rows in a k1a launch
         pre = os.environ.get("HBK_NO_PREFETCH") is None
 
@@ -662,23 +678,16 @@ class WakeWordTrainer(Trainer):
 
         def graph_of(n: int) -> "torch.cuda.CUDAGraph":
             """The captured graph of n (even) steps from the current parity."""
-            key = ("indexed", n, self._parity, B, y_stride, float(threshold), float(activation_threshold), float(p),
-                   defer, pre, ptrs, torch.cuda.current_stream(dev).cuda_stream)
-            entry = self._graphs.get(key)
-            if entry is not None:
-                return entry[0]
-            self._evict_graphs()
-            side, keep = capture_stream(dev)  # the replay stream's CU mask, if any
-            side.wait_stream(torch.cuda.current_stream(dev))
-            gr = torch.cuda.CUDAGraph()
             par0 = self._parity
-            with torch.cuda.stream(side):
-                with torch.cuda.graph(gr, stream=side):
-                    for j in range(n):
-                        one(par0 ^ (j & 1), True)
-            torch.cuda.current_stream(dev).wait_stream(side)
-            self._graphs[key] = (gr, ws, keep)  # the entry keeps the baked-in workspace alive
-            return gr
+            key = ("indexed", n, par0, B, y_stride, float(threshold), float(activation_threshold), float(p),
+                   defer, pre, ptrs, torch.cuda.current_stream(dev).cuda_stream)
+
+            def steps() -> None:
+                for j in range(n):
+                    one(par0 ^ (j & 1), True)
+
+            # the entry keeps the baked-in workspace alive; captured under the replay stream's CU mask, if any
+            return self._captured(key, lambda: (ws, [steps]), masked=True)[1][0]
 
         if graphs and distributed.graph_capturable(world) and S - done >= 2:
             # k-step graphs, then one graph for the even remainder: at most one
@@ -702,30 +711,49 @@ class WakeWordTrainer(Trainer):
     _MAX_GRAPHS = 16  # (a 3-stage call: ~2 step graphs per stage and parity, kept across calls)
 
     def _state_ptrs(self) -> tuple:
-        """Addresses a captured step bakes in besides its own buffers: the flat
-        parameters, Adam moments, gradient bucket and step state. Part of every
-        graph key, so a re-flattened or moved model never replays into freed
-        memory."""
+        """Addresses a captured step bakes in besides its own buffers: the flat parameters,
+        Adam moments, gradient bucket and step state. Part of every graph key, so a
+        re-flattened or moved model never replays into freed memory."""
         return tuple(t.data_ptr() for t in (self.model.flat_parameters, self._m, self._v, self._bucket,
                                             self._fstate))
 
     def _evict_graphs(self) -> None:
-        """Bound the capture cache: each captured graph holds its staging
-        buffers, workspace and memory pool, and the per-epoch keys (history
-        buffer, stage batch size) would otherwise accumulate for the
-        trainer's lifetime. Oldest captures go first."""
+        """Bound the capture cache: each captured graph holds its staging buffers,
+        workspace and memory pool, and the per-epoch keys (history buffer, stage batch
+        size) would otherwise accumulate for the trainer's lifetime. Oldest go first."""
         while len(self._graphs) >= self._MAX_GRAPHS:
             self._graphs.pop(next(iter(self._graphs)))
+
+    def _drop_step_graphs(self) -> None:
+        """Forget the per-batch loop's step graphs: every key but train_indexed's ("indexed", ...)."""
+        for key in [k for k in self._graphs if k[0] != "indexed"]:
+            del self._graphs[key]
+
+    def _history_buffer(self, steps: int) -> torch.Tensor:
+        """The per-step device record, regrown (and the step graphs that bake in its address dropped)."""
+        if self._history is None or self._history.shape[0] < steps:
+            self._history = torch.zeros((max(steps, 1), 8), dtype=torch.float32, device=self.device)
+            self._drop_step_graphs()
+        return self._history
+
+    def _epoch_buffers(self, idx: torch.Tensor, y: torch.Tensor) -> Tuple[torch.Tensor, ...]:
+        """_IndexedEpoch's (idx, y, sched), persistent per idx shape: the hipGraphs captured now bake in these
+        addresses, and later epochs and __call__s replay them (a capture per stage per call cost ~20 ms of
+        bench.py's 3-stage cli_path)."""
+        bufs = self._epoch_bufs.get(tuple(idx.shape))
+        if bufs is None:
+            sched = torch.zeros((max(idx.shape[0], 1), 2), dtype=torch.float32, device=idx.device)
+            bufs = self._epoch_bufs[tuple(idx.shape)] = (torch.empty_like(idx), torch.empty_like(y), sched)
+        return bufs
 
     def _graph_step(self, x: torch.Tensor, y: torch.Tensor, lr: float, neg_weight: float, threshold: float,
                     activation_threshold: float, history: Optional[torch.Tensor], seed: int, p: float,
                     world: int) -> None:
-        """The same step as two captured hipGraphs (forward/loss/backward, then gate +
-        Adam; the all-reduce runs between them when world > 1). lr, neg_weight and
-        the dropout seed change every step, so the kernels read them from a device
-        float64 [3] (hbk_mlp_set_step_scalars) filled before each replay. One
-        capture per (batch size, thresholds, dropout p, buffers): ~45 launches per
-        step become 2 graph launches + 3 fills + the batch copies."""
+        """The same step as two captured hipGraphs (forward/loss/backward, then gate + Adam;
+        the all-reduce runs between them when world > 1). lr, neg_weight and the dropout
+        seed change every step, so the kernels read them from a device float64 [3]
+        (hbk_mlp_set_step_scalars) filled before each replay. One capture per (batch size, thresholds,
+        dropout p, buffers): ~45 launches per step become 2 graph launches + 3 fills + the batch copies."""
         dev = self.device
         plan = self.model.plan
         flat = self.model.flat_parameters
@@ -733,52 +761,43 @@ class WakeWordTrainer(Trainer):
         key = (B, float(threshold), float(activation_threshold), float(p), world,
                tuple(t.data_ptr() for t in (flat, self._m, self._v, self._state, self._ctrl, self._bucket)),
                None if history is None else (history.data_ptr(), history.shape[0]))
-        graphs = self._graphs
-        g = graphs.get(key)
-        if g is None:
-            self._evict_graphs()
-            if getattr(self, "_scalars", None) is None or self._scalars.device != dev:
-                self._scalars = torch.zeros(3, dtype=torch.float64, device=dev)
+        if self._scalars is None:
+            self._scalars = torch.zeros(3, dtype=torch.float64, device=dev)
+
+        def make():
             sx = torch.zeros((B, plan.d_in), dtype=torch.float32, device=dev)
             sy = torch.zeros(B, dtype=torch.float32, device=dev)
-            # the graph owns its workspace: the plan's shared eager one may be
-            # reallocated by a larger (validation) batch after the capture
+            # its own workspace: a larger (validation) batch may reallocate the plan's shared eager one
             ws = torch.empty(plan.workspace_bytes(B), dtype=torch.uint8, device=dev)
-            side = torch.cuda.Stream(dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            fwd, upd = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-            plan.set_step_scalars(self._scalars)
-            try:
-                with torch.cuda.graph(fwd, stream=side):
-                    plan.train_fwd_bwd(flat, sx, sy, self._bucket, 1.0, threshold, activation_threshold,
-                                       dropout_p=p, seed=0, workspace=ws)
-                with torch.cuda.graph(upd, stream=side):
-                    plan.gate_adam(flat, self._bucket, self._m, self._v, self._state, self._ctrl, history,
-                                   1.0, BETAS[0], BETAS[1], EPS)
-            finally:
-                plan.set_step_scalars(None)  # eager launches keep their by-value arguments
-            torch.cuda.current_stream(dev).wait_stream(side)
-            g = graphs[key] = {"x": sx, "y": sy, "ws": ws, "fwd": fwd, "upd": upd}
-        g["x"].copy_(x.reshape(B, -1), non_blocking=True)
-        g["y"].copy_(y, non_blocking=True)
+            return (sx, sy, ws), [
+                lambda: plan.train_fwd_bwd(flat, sx, sy, self._bucket, 1.0, threshold, activation_threshold,
+                                           dropout_p=p, seed=0, workspace=ws),
+                lambda: plan.gate_adam(flat, self._bucket, self._m, self._v, self._state, self._ctrl, history,
+                                       1.0, BETAS[0], BETAS[1], EPS)]
+
+        plan.set_step_scalars(self._scalars)  # while set, launches (here: a capture's) read it
+        try:
+            (sx, sy, _), (fwd, upd) = self._captured(key, make)
+        finally:
+            plan.set_step_scalars(None)  # eager launches keep their by-value arguments
+        sx.copy_(x.reshape(B, -1), non_blocking=True)
+        sy.copy_(y, non_blocking=True)
         self._scalars[0].fill_(float(lr))
         self._scalars[1].fill_(float(neg_weight))
         self._scalars[2].fill_(float(seed))  # < 2^53: exact in float64
-        g["fwd"].replay()
+        fwd.replay()
         distributed.reduce_bucket(self._bucket)
-        g["upd"].replay()
+        upd.replay()
 
     @torch.no_grad()
     def _cat_pools(self, tensors: List[torch.Tensor]):
         """(pool32, pool16, {id(tensor): row offset}) for device datasets of both
-        dtypes: each dtype's distinct tensors as [n, 1536] rows, concatenated once and
-        cached (a single tensor of a dtype is used in place)."""
-        key = tuple((id(t), t.data_ptr(), t.shape[0], t.dtype) for t in tensors)
-        cache = getattr(self, "_pool_cache", None)
-        if cache is not None and cache[0] == key:
-            return cache[1]
-        out: List[Optional[torch.Tensor]] = []
-        off: Dict[int, int] = {}
+        dtypes: each dtype's distinct tensors as [n, 1536] rows, concatenated once (a
+        single contiguous tensor of a dtype is used in place). The copies are cached while
+        ``tensors`` are the same live, unwritten objects; the cache holds no caller's pool."""
+        hit = self._pool_cache is not None and _same_live(self._pool_cache[0], tensors)
+        cats: Dict[torch.dtype, torch.Tensor] = self._pool_cache[1] if hit else {}
+        out, off = [], {}
         for dt in (torch.float32, torch.float16):
             uniq = list({id(t): t for t in tensors if t.dtype == dt}.values())
             o = 0
@@ -786,39 +805,41 @@ class WakeWordTrainer(Trainer):
                 off[id(t)] = o
                 o += int(t.shape[0])
             rows = [t.reshape(t.shape[0], -1) for t in uniq]
-            out.append(None if not rows else rows[0].contiguous() if len(rows) == 1 else torch.cat(rows).contiguous())
-        res = (out[0], out[1], off)
-        self._pool_cache = (key, res)
-        return res
+            copy = len(rows) > 1 or (len(rows) == 1 and not rows[0].is_contiguous())
+            if copy and dt not in cats:
+                cats[dt] = torch.cat(rows).contiguous()
+            out.append(cats[dt] if copy else rows[0] if rows else None)
+        if not hit:
+            self._pool_cache = (_live_key(tensors), cats)
+        return out[0], out[1], off
 
     def _eval_from_iterators(self, validation: Any, testing: Any) -> "EvalPasses":
         """EvalPasses over device-pool validation / testing iterators (batches of
         their per-dataset counts, max_samples batches per pass; several datasets of a
-        side are concatenated once)."""
-        def side(it, label):
-            ds = [(d.data, n) for d, n, lab in _device_pools(it) if lab == label]
-            if not ds:
-                return None, 0
-            rows = [t.reshape(t.shape[0], -1) for t, _ in ds]
+        side are concatenated once). One EvalPasses (offsets, n and history carrying on)
+        serves while the iterators are the same live objects over the same live, unwritten
+        pool tensors, counts and max_samples; a pool that dies takes the passes with it."""
+        its = [it for it in (validation, testing) if it is not None]
+        pools = [[(d.data, n, lab) for d, n, lab in _device_pools(it)] for it in its]
+        live = its + [t for ps in pools for t, _, _ in ps]
+        meta = [(it.max_samples, [(n, lab) for _, n, lab in ps]) for it, ps in zip(its, pools)]
+        if self._eval_cache is not None and self._eval_cache[1] == meta and _same_live(self._eval_cache[0], live):
+            return self._eval_cache[2]
+
+        def side(ps, label):  # (the label's rows, its per-batch count); _IndexedEpoch.make saw both labels
+            rows = [t.reshape(t.shape[0], -1) for t, _, lab in ps if lab == label]
             dt = torch.float16 if all(t.dtype == torch.float16 for t in rows) else torch.float32
             pool = rows[0].contiguous() if len(rows) == 1 else torch.cat([r.to(dt) for r in rows]).contiguous()
-            return pool, sum(n for _, n in ds)
-        key = (id(validation), id(testing))
-        cache = getattr(self, "_eval_cache", None)
-        if cache is not None and cache[0] == key:
-            return cache[1]
-        vp, npv = side(validation, 1)
-        vn, nnv = side(validation, 0)
+            return pool, sum(n for _, n, lab in ps if lab == label)
+        (vp, npv), (vn, nnv) = side(pools[0], 1), side(pools[0], 0)
         kw: Dict[str, Any] = {}
         if testing is not None:
-            tp_, npt = side(testing, 1)
-            ta, nat = side(testing, 0)
-            if tp_ is not None and ta is not None:
-                kw = dict(testing_positive=tp_, testing_adversarial=ta, testing_batch=(npt, nat),
-                          testing_batches=testing.max_samples)
+            (tp_, npt), (ta, nat) = side(pools[1], 1), side(pools[1], 0)
+            kw = dict(testing_positive=tp_, testing_adversarial=ta, testing_batch=(npt, nat),
+                      testing_batches=testing.max_samples)
         ev = EvalPasses(self, vp, vn, validation_batch=(npv, nnv), validation_batches=validation.max_samples,
                         adjust_ratio=None, seed=random.getrandbits(31), **kw)
-        self._eval_cache = (key, ev)
+        self._eval_cache = (_live_key(live, lambda _dead: setattr(self, "_eval_cache", None)), meta, ev)
         return ev
 
     def _predict_all(self, data: Any) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -859,20 +880,19 @@ class WakeWordTrainer(Trainer):
             raise ValueError("train_epoch: with an EvalPasses validation the testing pass runs from its "
                              "testing pools (EvalPasses(..., testing=...)); pass testing=None")
         self._reset_accumulation(salt=random.getrandbits(24))
-        cap = getattr(self, "_history", None)
-        if cap is None or cap.shape[0] < num_steps or cap.device != self.device:
-            self._history = torch.zeros((max(num_steps, 1), 8), dtype=torch.float32, device=self.device)
-            self._graphs = {k: v for k, v in self._graphs.items() if k[0] == "indexed"}
-        history = self._history
+        history = self._history_buffer(num_steps)
         history.zero_()
+
+        def adjusted(weight: Union[float, List[float]], fph: float) -> float:  # the dynamic negative weight
+            assert isinstance(weight, float), \
+                "Negative weight schedule must be a float when using dynamic negative weight adjustment."
+            ratio = negative_weight_adjust_ratio
+            return weight * ratio if fph > target_false_positive_rate else max(1.0, weight / ratio)
+
         lr_hist: List[float] = []
         nw_hist: List[float] = []
         batch_sizes: List[int] = []
-        v_fp: List[float] = []
-        v_rec: List[float] = []
-        t_acc: List[float] = []
-        t_rec: List[float] = []
-        t_fp: List[float] = []
+        v_fp, v_rec, t_acc, t_rec, t_fp = [], [], [], [], []  # validation / testing histories (floats)
         seed0 = random.getrandbits(31)
         # device-pool iterators (the CLI's): the stage as device-sampled indexed steps in
         # hipGraph segments (train_indexed) between the validation / checkpoint points, the
@@ -926,12 +946,7 @@ class WakeWordTrainer(Trainer):
                         t_rec.append(vals[3])
                         t_acc.append(vals[4])
                     if negative_weight_adjust_ratio is not None:
-                        assert isinstance(negative_weight_schedule, float), \
-                            "Negative weight schedule must be a float when using dynamic negative weight adjustment."
-                        if fph > target_false_positive_rate:
-                            negative_weight_schedule = negative_weight_schedule * negative_weight_adjust_ratio
-                        else:
-                            negative_weight_schedule = max(1.0, negative_weight_schedule / negative_weight_adjust_ratio)
+                        negative_weight_schedule = adjusted(negative_weight_schedule, fph)
                 elif validation is not None:
                     preds, labels = self._predict_all(validation)
                     n_neg = int((labels == 0).sum().item())
@@ -944,12 +959,7 @@ class WakeWordTrainer(Trainer):
                     v_rec.append(_recall(float((preds[pos] > activation_threshold).sum().item()),
                                          float(pos.sum().item())))
                     if negative_weight_adjust_ratio is not None:
-                        assert isinstance(negative_weight_schedule, float), \
-                            "Negative weight schedule must be a float when using dynamic negative weight adjustment."
-                        if fph > target_false_positive_rate:
-                            negative_weight_schedule = negative_weight_schedule * negative_weight_adjust_ratio
-                        else:
-                            negative_weight_schedule = max(1.0, negative_weight_schedule / negative_weight_adjust_ratio)
+                        negative_weight_schedule = adjusted(negative_weight_schedule, fph)
                 if testing is not None and not isinstance(validation, EvalPasses):
                     preds, labels = self._predict_all(testing)
                     n_neg = max(int((labels == 0).sum().item()), 1)
@@ -958,22 +968,15 @@ class WakeWordTrainer(Trainer):
                     t_rec.append(_recall(float((preds[pos] > activation_threshold).sum().item()),
                                          float(pos.sum().item())))
                     t_acc.append(float(((preds > activation_threshold).float() == labels.float()).float().mean().item()))
-            elif v_fp or t_acc:
+            else:  # no pass at this step: the last pass's values, before the first one the caller's
+                had = bool(v_fp or t_acc)
                 if validation is not None:
-                    v_fp.append(v_fp[-1])
-                    v_rec.append(v_rec[-1])
+                    v_fp.append(v_fp[-1] if had else last_validation_false_positive_per_hour)
+                    v_rec.append(v_rec[-1] if had else last_validation_recall)
                 if testing is not None or (isinstance(validation, EvalPasses) and validation.testing):
-                    t_fp.append(t_fp[-1])
-                    t_rec.append(t_rec[-1])
-                    t_acc.append(t_acc[-1])
-            else:
-                if validation is not None:
-                    v_fp.append(last_validation_false_positive_per_hour)
-                    v_rec.append(last_validation_recall)
-                if testing is not None or (isinstance(validation, EvalPasses) and validation.testing):
-                    t_fp.append(last_testing_false_positive_rate)
-                    t_rec.append(last_testing_recall)
-                    t_acc.append(last_testing_accuracy)
+                    t_fp.append(t_fp[-1] if had else last_testing_false_positive_rate)
+                    t_rec.append(t_rec[-1] if had else last_testing_recall)
+                    t_acc.append(t_acc[-1] if had else last_testing_accuracy)
             if step > 0 and step % checkpoint_steps == 0:
                 self.save_checkpoint(f"{name}_{step}")
         if fast is not None:
@@ -1050,10 +1053,9 @@ class WakeWordTrainer(Trainer):
         hist: Dict[str, List[torch.Tensor]] = {k: [] for k in ("lr", "nw", "loss", "hlr", "recall", "fp", "vfp",
                                                                "vrecall", "tacc", "trecall", "tfp")}
         last = {"loss": 0.0, "recall": 0.0, "fp": 0.0, "vfp": 0.0, "vrec": 0.0, "tacc": 0.0, "trec": 0.0, "tfp": 0.0}
-        for hook in ("start",):
-            for d in (training, validation, testing):
-                if hasattr(d, hook):
-                    getattr(d, hook)()
+        for d in (training, validation, testing):
+            if hasattr(d, "start"):
+                d.start()
         # the per-step history buffer sized once for the longest stage: train_indexed's hipGraphs
         # bake in its address, so a buffer regrown by a later stage made every stage of the next
         # call capture its graphs again (6 captures, ~28 ms of a 3-stage bench call)
@@ -1061,9 +1063,7 @@ class WakeWordTrainer(Trainer):
         for _ in range(num_stages - 1):
             n_ = max(validation_steps, int(n_ * step_adjust_ratio))
             n_max = max(n_max, n_)
-        cap = getattr(self, "_history", None)
-        if cap is None or cap.shape[0] < n_max or cap.device != self.device:
-            self._history = torch.zeros((max(n_max, 1), 8), dtype=torch.float32, device=self.device)
+        self._history_buffer(n_max)
         for i in range(num_stages):
             if dynamic_negative_weight:
                 weights: Union[float, List[float]] = max_negative_weight

@@ -344,3 +344,136 @@ def test_train_epoch_device_iterator_runs_indexed_and_equals_eager(tmp_path, mon
         np.testing.assert_allclose(hf[i].numpy(), he[i].numpy(), rtol=1e-5, atol=1e-5)
     d = (pf - pe).abs()
     assert float((d > 1e-5).float().mean()) < 1e-3 and float(d.max()) <= min(2e-2, 2 * float(he[0].sum()))
+
+
+# -- the trainer's data caches and captured graphs across epochs (shapes of the test above) --
+
+def _rows(rng, n, shift=0.0, half=False):
+    t = torch.from_numpy(rng.standard_normal((n, 16, 96)).astype(np.float32) + shift).cuda()
+    return t.half() if half else t
+
+
+def _epoch_trainer(tmp_path, params=None):
+    from heybuddy.trainer import WakeWordTrainer
+    tr = WakeWordTrainer(checkpoint_dir=str(tmp_path), device="cuda")
+    params = gc.golden_inputs()[0] if params is None else params
+    tr.model.load_state_dict({k: torch.from_numpy(v) for k, v in params.items()}, strict=True)
+    tr.model.dropout.p = 0.0
+    return tr
+
+
+def _iterators(pos, adv, neg, vpos, vneg, tpos, tadv):
+    from heybuddy.dataset.training import WakeWordTrainingDatasetIterator as It
+    dev = pos.device
+    return (It(positive=[(pos, 20)], negative=[(adv, 20), (neg, 100)], device=dev, seed=5),
+            It(positive=[(vpos, 50)], negative=[(vneg, 200)], device=dev, seed=6, max_samples=2),
+            It(positive=[(tpos, 20)], negative=[(tadv, 20)], device=dev, seed=7, max_samples=3))
+
+
+def _epoch(tr, training, val, tst, **kw):
+    h = tr.train_epoch(training, validation=val, testing=tst, num_steps=13, warmup_steps=3, hold_steps=3,
+                       validation_steps=5, checkpoint_steps=1000, negative_weight_schedule=2.0,
+                       negative_weight_adjust_ratio=2.0, target_false_positive_rate=1e6, **kw)
+    torch.cuda.synchronize()
+    return h
+
+
+def test_train_epoch_sees_replaced_validation_pools(tmp_path, monkeypatch):
+    """one trainer, one validation / testing iterator pair, and the
+    validation iterator's pools replaced between two epochs by DevicePools over other
+    tensors of the same shapes. The second epoch's passes must read the new tensors
+    (the addresses EvalPasses.run evaluates) and report their recall.
+
+    Every validation positive's logit changes sign between the epochs. The model's
+    input LayerNorm removes a constant shift of a row, and the golden weights' logits
+    on Gaussian rows are all negative (-0.97 .. -0.15), so the rows are chosen by the
+    float64 oracle instead: of 4,000 candidate rows the first epoch validates on the
+    100 with the highest logit, the second on the 100 with the lowest, and the output
+    bias is moved so that the candidates' median logit is 0 (the two groups then lie
+    more than 0.15 to either side of it; at lr 1e-5 the 26 Adam steps move no
+    parameter by more than 2.6e-4). Recall is therefore 1 at every validated step of
+    the first epoch and 0 at every one of the second; a stale EvalPasses reports 1
+    in both."""
+    from heybuddy import trainer as trm
+    from heybuddy.dataset.training import DevicePool
+    from oracle import mlp as omlp
+    rng = np.random.default_rng(8)
+    params = dict(gc.golden_inputs()[0])
+    cand = rng.standard_normal((4000, 16, 96)).astype(np.float32)
+    z = omlp.forward(params, cand)[1]
+    shift = float(np.median(z))
+    params["mlp_out.output.bias"] = (params["mlp_out.output.bias"] - shift).astype(np.float32)
+    z = z - shift
+    order = np.argsort(z)
+    print(f"logits: lowest 100 <= {z[order[99]]:.4f}, highest 100 >= {z[order[-100]]:.4f}")
+    assert z[order[99]] < -0.15 and z[order[-100]] > 0.15
+    tr = _epoch_trainer(tmp_path, params)
+    vpos1, vpos2 = torch.from_numpy(cand[order[-100:]]).cuda(), torch.from_numpy(cand[order[:100]]).cuda()
+    vneg1, vneg2 = _rows(rng, 400, half=True), _rows(rng, 400, half=True)
+    tpos, tadv = _rows(rng, 60, 0.4), _rows(rng, 60, -0.1)
+    training, val, tst = _iterators(_rows(rng, 300, 0.7), _rows(rng, 300, -0.2), _rows(rng, 2000, half=True),
+                                    vpos1, vneg1, tpos, tadv)
+    passes = []
+    orig = trm.EvalPasses.run
+    monkeypatch.setattr(trm.EvalPasses, "run", lambda self, *a, **k: (
+        passes.append([part[0].data_ptr() for part in self.parts]), orig(self, *a, **k))[1])
+    h1 = _epoch(tr, training, val, tst, learning_rate=1e-5)
+    assert passes == [[t.data_ptr() for t in (vpos1, vneg1, tpos, tadv)]] * 2
+    gen = val.positive[0][0].gen
+    val.positive, val.negative = [(DevicePool(vpos2, gen), 50)], [(DevicePool(vneg2, gen), 200)]
+    del passes[:]
+    h2 = _epoch(tr, training, val, tst, learning_rate=1e-5)
+    print("validation recall:", h1[7].tolist(), h2[7].tolist())
+    assert passes == [[t.data_ptr() for t in (vpos2, vneg2, tpos, tadv)]] * 2
+    assert h1[7][5:].tolist() == [1.0] * 8 and h2[7][5:].tolist() == [0.0] * 8
+
+
+def test_train_epoch_sees_refilled_training_pools(tmp_path, monkeypatch):
+    """two f32 training pools (positive, adversarial), which
+    _cat_pools concatenates into a copy. After an in-place refill of the positive
+    pool the next epoch (fresh iterators over the same tensors) must train on a
+    pool32 whose first rows are the new positives; with nothing changed, the epoch
+    after that reuses the very same pool32 (the hit the benchmark's stages rely on)."""
+    from heybuddy import trainer as trm
+    rng = np.random.default_rng(8)
+    tr = _epoch_trainer(tmp_path)
+    pos, adv, neg = _rows(rng, 300, 0.7), _rows(rng, 300, -0.2), _rows(rng, 2000, half=True)
+    ev = (_rows(rng, 100, 0.4), _rows(rng, 400, half=True), _rows(rng, 60, 0.4), _rows(rng, 60, -0.1))
+    seen = []
+    orig = trm.WakeWordTrainer.train_indexed
+    monkeypatch.setattr(trm.WakeWordTrainer, "train_indexed",
+                        lambda self, *a, **k: (seen.append(k["pool32"]), orig(self, *a, **k))[1])
+    _epoch(tr, *_iterators(pos, adv, neg, *ev))
+    assert torch.equal(seen[-1][:len(pos)].view_as(pos), pos) and torch.equal(seen[-1][len(pos):].view_as(adv), adv)
+    pos.copy_(_rows(rng, 300, -0.5))
+    del seen[:]
+    _epoch(tr, *_iterators(pos, adv, neg, *ev))
+    second = seen[-1]
+    assert len(seen) == 3 and all(p is second for p in seen)
+    assert torch.equal(second[:len(pos)].view_as(pos), pos)
+    _epoch(tr, *_iterators(pos, adv, neg, *ev))
+    assert len(seen) == 6 and all(p is second for p in seen)
+
+
+def test_train_epoch_unchanged_iterators_reuse_graphs_and_eval(tmp_path, monkeypatch):
+    """The same iterators over the same pools, epoch after epoch (the stages of a
+    __call__, bench.py's cli_path): the second epoch captures no graph and runs its
+    passes on the first epoch's EvalPasses, whose pass count carries on."""
+    from heybuddy import trainer as trm
+    rng = np.random.default_rng(8)
+    tr = _epoch_trainer(tmp_path)
+    its = _iterators(_rows(rng, 300, 0.7), _rows(rng, 300, -0.2), _rows(rng, 2000, half=True),
+                     _rows(rng, 100, 0.4), _rows(rng, 400, half=True), _rows(rng, 60, 0.4), _rows(rng, 60, -0.1))
+    captures, evals = [], []
+    begin = torch.cuda.CUDAGraph.capture_begin
+    monkeypatch.setattr(torch.cuda.CUDAGraph, "capture_begin",
+                        lambda self, *a, **k: (captures.append(1), begin(self, *a, **k))[1])
+    run = trm.EvalPasses.run
+    monkeypatch.setattr(trm.EvalPasses, "run", lambda self, *a, **k: (evals.append((self, self.n)), run(self, *a, **k))[1])
+    _epoch(tr, *its)
+    first, graphs = len(captures), len(tr._graphs)
+    print("captures in the first epoch:", first)
+    assert first == graphs >= 1  # every capture is one entry: the 4-step graph inside the segments of 6 and 5 steps
+    _epoch(tr, *its)
+    assert len(captures) == first and len(tr._graphs) == graphs
+    assert [n for _, n in evals] == [0, 1, 2, 3] and all(e is evals[0][0] for e, _ in evals)
