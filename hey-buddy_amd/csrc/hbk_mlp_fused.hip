@@ -21,7 +21,10 @@
 //              LayerNorm forward, sigmoid, the high-loss filter, weighted BCE
 //              statistics and dL/dz, then the backward chain down to dHG0;
 //              bias and LayerNorm(96) gradients as per-tile column sums
-//              (float atomics); activations for the weight gradients to HBM
+//              (float atomics); activations for the weight gradients to HBM.
+//              A tile none of whose rows the filter kept ends after the loss
+//              stage (zero gradient rows and maxima written), and the v2
+//              weight-gradient kernel k3s walks the other tiles only
 //   k3_wgrad   every weight gradient dW = dY^T X as split-K MFMA tiles with
 //              atomic accumulation into the gradient bucket; the input layer's
 //              tiles also produce the norm_in gamma/beta gradients from the
@@ -1284,6 +1287,30 @@ __global__ void __launch_bounds__(256) k2_rows_kernel(K2Args a) {
   K2_MARK(41);
   if (tid < kStats && red[tid] != 0.f) atomicAdd(BCK(a.stats + tid, 4), red[tid]);
   // ---------------------------------------------------------- backward ---
+  // A tile none of whose rows the high-loss filter kept (red[0], its count of selected rows: the
+  // same in every thread) has dz = 0 in every row, so every gradient it would compute is an
+  // exact zero: it skips the backward chain. What later kernels read unconditionally is written
+  // as the chain would have written it: zero dHG / dS rows (v1's k3 and the dense k3s walk every
+  // tile) and zero maxima (k3s tells a live tile by its max |dz|); the bias and LayerNorm
+  // gradients would have been atomic adds of zero.
+  if (!HBK_K2_ABLATE && red[0] == 0.f) {
+    const f4 z4 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < NG; ++k) {
+      for (int e = tid; e < 4 * kH2; e += 256) st4(a.dHG + k * kH2 * Bp, e >> 2, 4 * (e & 3), z4);
+      if (k + 1 < NG) {
+        for (int e = tid; e < 4 * kL; e += 256) st4(a.dS + k * kL * Bp, e >> 2, 4 * (e & 3), z4);
+      } else if (tid < 4) {
+        st4(a.dS + k * kL * Bp, 0, 4 * tid, z4);
+      }
+    }
+    if (a.maxS && lane == 0) {
+#pragma unroll
+      for (int mat = 0; mat < 2 * NG; ++mat)
+        *BCK(&a.maxS[(static_cast<int64_t>(mat) * a.n_rt + blockIdx.x) * 4 + wave], 4) = 0.f;
+    }
+    return;
+  }
   float* G = a.G;
   {
     const f4 dz4 = f4{dzS[4 * (tid & 3)], dzS[4 * (tid & 3) + 1], dzS[4 * (tid & 3) + 2], dzS[4 * (tid & 3) + 3]};
@@ -1704,7 +1731,25 @@ __global__ void __launch_bounds__(256) k3_wgrad_kernel(K3Args a) {
 // maxima (maxS), so the whole split accumulates in one scale. The input layer's X
 // is not stored anywhere: it is recomputed from the pool rows, k1s's statistics and
 // dropout mask (xhat = (v - mu) rs, the formula of k1a) as the chunk is staged.
+//
+// Live row tiles. The high-loss filter (trainer.py:407-424) keeps a small part of a trained
+// classifier's batch (the headline's 1,100 rows: median 101 kept), and a row it
+// drops has dz = 0: an exact zero in every gradient. k2 ends a 16-row tile without a kept row
+// after its loss stage (zero dHG / dS rows and zero maxima written), and k3s walks only the
+// tiles that hold a kept row: each workgroup lists them in ascending order in its prologue
+// (from k2's max |dz| per tile; a ballot and a prefix sum over 8 words, the same in every
+// workgroup, no atomics, read from device memory so that a replayed graph follows each step),
+// the job's S splits share the list's 32-row steps evenly, and a split's step count picks the
+// shortest of a few compiled, fully unrolled bodies by one uniform branch (the steps stay
+// straight-line code). A split past the list writes zero slabs, so k4 and k3_fold_kernel sum
+// all S slabs as before. The sums over the kept rows keep their ascending row order; with
+// every tile live the splits are the dense ones and the results have the dense path's bits,
+// otherwise rows move to other splits and the slab sum changes at rounding level.
+// Granularity is the 16-row tile (the loads stay contiguous 16-B runs along the batch), not the
+// row: a live tile's dropped rows are still multiplied as zeros. HBK_STEP_DENSE=1 walks every
+// tile (A/B runs), as does a batch of more than kK3sMaxTiles tiles.
 constexpr int kK3sMaxR = 512;  // rows per split
+constexpr int kK3sMaxTiles = 512;  // row tiles of a batch whose live tiles are listed (one thread each)
 // 8 waves of one 16-row M tile each: two waves per SIMD hide each other's latency (4 waves
 // of two M tiles ran one wave per SIMD at 256 VGPRs + AGPRs, 4.2 k cycles per 32-row step
 // against 1.9 k of issue). (4 M groups of two tiles x 2 column halves -- each B fragment read
@@ -1736,6 +1781,7 @@ struct K3sArgs {
   int64_t g_off, b_off;
   float* part;  // [S][pstride]
   int64_t pstride;
+  int sparse;  // 1: walk the live row tiles only (0: every tile; HBK_STEP_DENSE=1, or n_rt > kK3sMaxTiles)
 };
 // XOR swizzle of the 16-B chunks of a 256-B row (the input layer's [32][128] half images):
 // conflict-free ds_write_b128 of whole chunks and ds_read_b64_tr_b16 of the B operand
@@ -1757,6 +1803,8 @@ struct K3sShared {
   float red[2][kK3sWaves][16 * kK3sNbtRaw];
   uint4 rinfoS[kK3sMaxR];                          // input layer: the split's rows' {mu, rs, address}
   uint32_t maskS[kK3sMaxR * kK3sNbtRaw / 2];       // ... and their mask words of this N tile
+  unsigned long long balS[kK3sWaves];              // live row tiles: the waves' ballots ...
+  uint16_t tileS[kK3sMaxTiles];                    // ... and the ascending list of the live tiles
 };
 // one workgroup's tile; kRaw: the input layer (X from the pool rows). NST steps of 32 rows,
 // fully unrolled, the prefetches unconditional (clamped to the last step: a redundant
@@ -1766,7 +1814,7 @@ struct K3sShared {
 // computes zero rows in its tail steps.
 template <int NBT, bool kRaw, int NST>
 __device__ __forceinline__ void k3s_body(const K3sArgs& a, const K3sJob& jb, int split, int tm, int tnn,
-                                         K3sShared& sh) {
+                                         K3sShared& sh, int ct0, int cend) {
   constexpr int NT = 16 * NBT, kLdY = K3sShared::kLdY;
   constexpr int kYU = NT * 8 / kK3sThr;  // float4 units per thread and step (transposed X)
   constexpr int MT = kK3sMT, NBW = NBT;  // M tiles and column tiles per wave
@@ -1777,8 +1825,27 @@ __device__ __forceinline__ void k3s_body(const K3sArgs& a, const K3sJob& jb, int
   auto raw_off = [](int r, int c) { return (c >> 4) * (32 * 128) + r * 128 + 8 * k3s_swz(r, c & 15); };
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, m = lane & 15, kq = lane >> 4;
   const int Bp = static_cast<int>(a.Bp);
-  const int rb0 = split * jb.R;
   constexpr int nst = NST;
+  // the split's rows: the listed row tiles ct0 .. cend - 1 (0 < cend - ct0 <= 2 NST), two per
+  // 32-row step. tile_row: batch row of listed tile c's first row (c clamped to the split's last
+  // tile: a load past the split re-reads that tile, and is zeroed at use)
+  auto tile_row = [&](int c) {
+    c = min(c, cend - 1);
+    const int t = sh.tileS[min(c, kK3sMaxTiles - 1)];
+    return 16 * (a.sparse ? t : c);
+  };
+  // batch row of the split's row rl, and whether rl is a row (of a listed tile, below B)
+  auto row_of = [&](int rl) { return tile_row(ct0 + (rl >> 4)) + (rl & 15); };
+  auto row_ok = [&](int rl) { return ct0 + (rl >> 4) < cend && row_of(rl) < a.B; };
+  // The steps' loads take their tiles from a register: lane l holds the first row of the split's
+  // l-th tile (2 NST <= 32 tiles), and step u reads its two tiles by v_readlane at the constant
+  // lanes 2 u, 2 u + 1 (a list read per load kept an address per unrolled step in registers: 27
+  // VGPRs spilled at 5 / 12 steps). half: which of the step's two tiles this lane's rows are in
+  const int tl = tile_row(ct0 + lane);
+  auto step_row = [&](int u, int half) {
+    const int t0 = __builtin_amdgcn_readlane(tl, 2 * u), t1 = __builtin_amdgcn_readlane(tl, 2 * u + 1);
+    return half ? t1 : t0;
+  };
   const int n0 = tnn * NT;
   const int mg = wave, nt0 = 0;  // this wave's M group, first column tile
   const int mrow = tm * 128 + 16 * MT * mg;
@@ -1786,11 +1853,9 @@ __device__ __forceinline__ void k3s_body(const K3sArgs& a, const K3sJob& jb, int
   const float* Xt[MT];
 #pragma unroll
   for (int t = 0; t < MT; ++t) Xt[t] = jb.X + static_cast<int64_t>(min(mrow + 16 * t + m, jb.M - 1)) * Bp;
-  // (unclamped: rows past Bp read the next row, or past the last row of the workspace array the
-  // arrays after it, <= R floats; they are zeroed at use. One base address per tile and
-  // immediate offsets per step: a clamp per step held a 64-bit address per unrolled step)
+  // (lane (m, kq) of step u: rows 8 (kq & 1) .. + 7 of the step's listed tile kq >> 1)
   auto load_g = [&](int u, f4 (&d)[MT][2]) {
-    const int b = rb0 + 32 * u + 8 * kq;
+    const int b = step_row(u, kq >> 1) + 8 * (kq & 1);
 #pragma unroll
     for (int h = 0; h < 2; ++h)
 #pragma unroll
@@ -1819,7 +1884,7 @@ __device__ __forceinline__ void k3s_body(const K3sArgs& a, const K3sJob& jb, int
 #pragma unroll
       for (int jj = 0; jj < kYU; ++jj) {
         const int q = tid + kK3sThr * jj, col = min(n0 + (q >> 3), jb.N - 1);
-        const int b = rb0 + 32 * u + 4 * (q & 7);  // (unclamped, as the gradient's)
+        const int b = step_row(u, (q & 7) >> 2) + 4 * (q & 3);
         yv[ys_][jj] = *BCK(reinterpret_cast<const f4*>(jb.Y + static_cast<int64_t>(col) * Bp + b), 16);
       }
     }
@@ -1838,7 +1903,7 @@ __device__ __forceinline__ void k3s_body(const K3sArgs& a, const K3sJob& jb, int
         const uint4 inf = sh.rinfoS[rl];
         const bool is16 = (inf.z & 1u) != 0;
         const uint32_t bits = sh.maskS[rl * (NT / 32) + (ch >> 2)] >> (8 * (ch & 3));
-        const float mu = __uint_as_float(inf.x), rs = rb0 + rl < a.B ? __uint_as_float(inf.y) : 0.f;
+        const float mu = __uint_as_float(inf.x), rs = __uint_as_float(inf.y);  // (staged as 0 where rl is no row)
         const uint4 lo = ylo[ys_][j], hi = yhi[ys_][j];
         const uint32_t hw[4] = {lo.x, lo.y, lo.z, lo.w};
         const uint32_t fw[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
@@ -1863,7 +1928,7 @@ __device__ __forceinline__ void k3s_body(const K3sArgs& a, const K3sJob& jb, int
 #pragma unroll
       for (int jj = 0; jj < kYU; ++jj) {
         const int q = tid + kK3sThr * jj, col = q >> 3, b4 = 4 * (q & 7);
-        const f4 v = rb0 + 32 * u + b4 < Bp ? yv[ys_][jj] : f4{0.f, 0.f, 0.f, 0.f};
+        const f4 v = ct0 + 2 * u + (b4 >> 4) < cend ? yv[ys_][jj] : f4{0.f, 0.f, 0.f, 0.f};
         uint32_t h0, l0, h1, l1;
         split_pair(v[0], v[1], h0, l0);
         split_pair(v[2], v[3], h1, l1);
@@ -1890,11 +1955,12 @@ __device__ __forceinline__ void k3s_body(const K3sArgs& a, const K3sJob& jb, int
   static_assert(kK3sMaxR / 16 * 4 <= 128, "maxS: two entries per lane");
   float mxv[2];
   {
-    const int t0 = rb0 / 16, n4 = 4 * (min(a.n_rt, (rb0 + 32 * nst) / 16) - t0);
+    const int n4 = 4 * (cend - ct0);
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int q = lane + 64 * i;
-      const float v = *BCK(&a.maxS[(static_cast<int64_t>(jb.mat) * a.n_rt + t0) * 4 + min(q, n4 - 1)], 4);
+      const int t = tile_row(ct0 + (q >> 2)) >> 4;
+      const float v = *BCK(&a.maxS[(static_cast<int64_t>(jb.mat) * a.n_rt + t) * 4 + (q & 3)], 4);
       mxv[i] = q < n4 ? v : 0.f;
     }
   }
@@ -1910,16 +1976,16 @@ __device__ __forceinline__ void k3s_body(const K3sArgs& a, const K3sJob& jb, int
     uint32_t mi[kMI];
 #pragma unroll
     for (int it = 0; it < kRI; ++it)
-      ri[it] = *BCK(&a.rinfo[min(rb0 + min(tid + kK3sThr * it, nr - 1), a.B - 1)], 16);
+      ri[it] = *BCK(&a.rinfo[min(row_of(min(tid + kK3sThr * it, nr - 1)), a.B - 1)], 16);
 #pragma unroll
     for (int v = 0; v < 2; ++v)
 #pragma unroll
       for (int j = 0; j < kCPT; ++j)
-        r01[v][j] = *BCK(&a.rinfo[min(rb0 + 32 * min(v, last) + (tid + kK3sThr * j) / kCPR, a.B - 1)], 16);
+        r01[v][j] = *BCK(&a.rinfo[min(row_of(32 * min(v, last) + (tid + kK3sThr * j) / kCPR), a.B - 1)], 16);
 #pragma unroll
     for (int it = 0; it < kMI; ++it) {
       const int q = min(tid + kK3sThr * it, nr * (NT / 32) - 1);
-      mi[it] = *BCK(&a.mask[static_cast<int64_t>(min(rb0 + q / (NT / 32), a.B - 1)) * kMaskW + n0 / 32 + q % (NT / 32)], 4);
+      mi[it] = *BCK(&a.mask[static_cast<int64_t>(min(row_of(q / (NT / 32)), a.B - 1)) * kMaskW + n0 / 32 + q % (NT / 32)], 4);
     }
 #pragma unroll
     for (int v = 0; v < 2; ++v)
@@ -1928,7 +1994,10 @@ __device__ __forceinline__ void k3s_body(const K3sArgs& a, const K3sJob& jb, int
     pow2_scale(wmax(fmaxf(mxv[0], mxv[1])), sc, inv);
 #pragma unroll
     for (int it = 0; it < kRI; ++it)
-      if (tid + kK3sThr * it < nr) sh.rinfoS[tid + kK3sThr * it] = ri[it];
+      if (tid + kK3sThr * it < nr) {
+        if (!row_ok(tid + kK3sThr * it)) ri[it].y = 0u;  // rs = 0: its xhat is 0
+        sh.rinfoS[tid + kK3sThr * it] = ri[it];
+      }
 #pragma unroll
     for (int it = 0; it < kMI; ++it)
       if (tid + kK3sThr * it < nr * (NT / 32)) sh.maskS[tid + kK3sThr * it] = mi[it];
@@ -1945,8 +2014,8 @@ __device__ __forceinline__ void k3s_body(const K3sArgs& a, const K3sJob& jb, int
   __syncthreads();
   HBK_MT(2, 4);
   auto step = [&](int u, f4 (&g)[MT][2]) {
-    // this step's gradient: dead batch rows zeroed, row sums (input layer), scaled split
-    const bool live = rb0 + 32 * u + 8 * kq < Bp;
+    // this step's gradient: rows past the split's tiles zeroed, row sums (input layer), scaled split
+    const bool live = ct0 + 2 * u + (kq >> 1) < cend;
     h8 ah[MT], al[MT];
 #pragma unroll
     for (int t = 0; t < MT; ++t) {
@@ -2126,10 +2195,76 @@ __global__ void __launch_bounds__(kK3sThr, kOcc) k3s_kernel(K3sArgs a) {
   const int tm = tile / jb.tn, tnn = tile - tm * jb.tn;
   HBK_MT(2, 1);
   HBK_SPAN(0, __builtin_amdgcn_s_memrealtime());
-  if (jb.Y == nullptr)
-    k3s_body<kK3sNbtRaw, true, NST0>(a, jb, split, tm, tnn, sh);
-  else
-    k3s_body<kK3sNbtGen, false, NST1>(a, jb, split, tm, tnn, sh);
+  // The live row tiles. A row the high-loss filter dropped has dz = 0 and adds an exact zero to
+  // every weight gradient, so a 16-row tile whose rows are all dropped is not walked at all: it
+  // is told by k2's published max |dz| of the tile (maxS of the last job's matrix, dS_{NG-1},
+  // whose row 0 is dz; a selected row's dz = w (p - y) is never 0). Every workgroup lists the
+  // live tiles in ascending order (one thread per tile, wave ballots, prefix over the 8 words:
+  // the same list everywhere, no atomics), and the job's S splits share the list's 32-row steps
+  // evenly, q = ceil(steps / S) each, so the sums keep the ascending row order. A split past
+  // the list writes its slab(s) as zeros: k4 and k3_fold go on summing all S slabs.
+  int n_live = a.n_rt, q = jb.R / 32;
+  if (a.sparse) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    bool lv = false;
+    if (tid < a.n_rt) {
+      const f4 v = *BCK(reinterpret_cast<const f4*>(a.maxS + (static_cast<int64_t>(a.n_jobs - 1) * a.n_rt + tid) * 4), 16);
+      lv = v[0] != 0.f || v[1] != 0.f || v[2] != 0.f || v[3] != 0.f;
+    }
+    const unsigned long long bal = __ballot(lv);
+    if (lane == 0) sh.balS[wave] = bal;
+    __syncthreads();
+    int pos = __popcll(bal & ((1ull << lane) - 1ull));
+    n_live = 0;
+#pragma unroll
+    for (int w = 0; w < kK3sWaves; ++w) {
+      const int c = __popcll(sh.balS[w]);
+      pos += w < wave ? c : 0;
+      n_live += c;
+    }
+    if (lv) sh.tileS[pos] = static_cast<uint16_t>(tid);
+    __syncthreads();
+    q = ((n_live + 1) / 2 + jb.S - 1) / jb.S;
+  }
+  const int ct0 = 2 * split * q, cend = min(ct0 + 2 * q, n_live);
+  if (ct0 >= cend) {  // (uniform) no live tile for this split: zero slab(s)
+    const bool raw = jb.Y == nullptr;
+    const int NT = 16 * (raw ? kK3sNbtRaw : kK3sNbtGen), n0 = tnn * NT;
+    float* const C = a.part + split * a.pstride + jb.c_off;
+    for (int e = threadIdx.x; e < 128 * NT; e += kK3sThr) {
+      const int row = tm * 128 + e / NT, c = n0 + e % NT;
+      if (row < jb.M && c < jb.N)
+        for (int z = split; z < a.S; z += jb.S)  // (and the slabs past this job's splits)
+          *BCK(&C[(z - split) * a.pstride + static_cast<int64_t>(row) * jb.ldc + c], 4) = 0.f;
+    }
+    if (raw && static_cast<int>(threadIdx.x) < NT) {
+      float* P = a.part + split * a.pstride;
+      *BCK(&P[a.g_off + n0 + threadIdx.x], 4) = 0.f;
+      *BCK(&P[a.b_off + n0 + threadIdx.x], 4) = 0.f;
+    }
+    return;
+  }
+  // the shortest compiled (fully unrolled, straight-line) step count that holds the split's q steps
+  constexpr int kA0 = 1, kB0 = 2, kC0 = 3, kA1 = 2, kB1 = 4, kC1 = 8;
+  if (jb.Y == nullptr) {
+    if (kA0 < NST0 && q <= kA0)
+      k3s_body<kK3sNbtRaw, true, kA0 < NST0 ? kA0 : NST0>(a, jb, split, tm, tnn, sh, ct0, cend);
+    else if (kB0 < NST0 && q <= kB0)
+      k3s_body<kK3sNbtRaw, true, kB0 < NST0 ? kB0 : NST0>(a, jb, split, tm, tnn, sh, ct0, cend);
+    else if (kC0 < NST0 && q <= kC0)
+      k3s_body<kK3sNbtRaw, true, kC0 < NST0 ? kC0 : NST0>(a, jb, split, tm, tnn, sh, ct0, cend);
+    else
+      k3s_body<kK3sNbtRaw, true, NST0>(a, jb, split, tm, tnn, sh, ct0, cend);
+  } else {
+    if (kA1 < NST1 && q <= kA1)
+      k3s_body<kK3sNbtGen, false, kA1 < NST1 ? kA1 : NST1>(a, jb, split, tm, tnn, sh, ct0, cend);
+    else if (kB1 < NST1 && q <= kB1)
+      k3s_body<kK3sNbtGen, false, kB1 < NST1 ? kB1 : NST1>(a, jb, split, tm, tnn, sh, ct0, cend);
+    else if (kC1 < NST1 && q <= kC1)
+      k3s_body<kK3sNbtGen, false, kC1 < NST1 ? kC1 : NST1>(a, jb, split, tm, tnn, sh, ct0, cend);
+    else
+      k3s_body<kK3sNbtGen, false, NST1>(a, jb, split, tm, tnn, sh, ct0, cend);
+  }
   HBK_SPAN(1, __builtin_amdgcn_s_memrealtime());
   HBK_SPAN(2, (static_cast<unsigned long long>(j) << 32) | split);
 }
@@ -3478,6 +3613,9 @@ int mlp_fused_run(const hbk_mlp_plan& p, const float* params, const float* pool3
     k3.b_off = p.ln_in.b;
     k3.part = ws + w.part;
     k3.pstride = w.pstride;
+    // HBK_STEP_DENSE=1 (A/B runs): every row tile is walked, as before the live-tile list
+    static const bool dense = env_int("HBK_STEP_DENSE", 0) != 0;
+    k3.sparse = !dense && rt <= kK3sMaxTiles ? 1 : 0;
     launch_k3s(pl.pair, dim3(wgs), s, k3);
     HBK_LAUNCH_CHECK("k3s_kernel");
     if (flags & HBK_STEP_DEFER_PARTIALS) {

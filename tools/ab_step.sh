@@ -9,9 +9,10 @@ mkdir -p gpurun_out
 for C in ${CUS:-64}; do
 for V in ${VARIANTS:-HBK_STEP=2}; do
   T=gpurun_out/abs_$(echo "$V" | tr '=,' '__')_$C
+  T=${T%%/*}/$(echo "${T#*/}" | tr '/' '_')  # (a variant that names a path, e.g. HBK_LIB=dir/lib.so)
   rm -rf $T
   env $(echo "$V" | tr ',' ' ') timeout -k 10 200 rocprofv3 --kernel-trace --stats -f csv -d $T -o run -- python3 tools/probe_mlp.py ${STEPS:-200} --cus=$C --batch=${BATCH:-1100} > $T.log 2>&1 || { tail -5 $T.log; exit 1; }
-  echo "== $V ($C CUs; 0 = all; B=${BATCH:-1100}): $(grep 'us per train' $T.log)"
+  echo "== $V ($C CUs; 0 = all; B=${BATCH:-1100}): $(grep -e 'us per train' -e 'n_sel of' $T.log)"
   python3 - $T <<'PY'
 import csv, glob, sys
 f = glob.glob(sys.argv[1] + "/**/*kernel_stats.csv", recursive=True)[0]

@@ -71,6 +71,9 @@ def timing(S, n_cus=0):
     torch.cuda.synchronize()
     print(f"{e0.elapsed_time(e1) * 1e3 / (3 * S):.2f} us per train step (B={BATCH}, {S} steps x 3"
           f"{', captured 1-rank all-reduce' if '--reduce' in sys.argv else ''})")
+    n_sel = hist[:, 0].cpu().numpy()  # the last pass's rows the high-loss filter kept, per step
+    print(f"  n_sel of the last {S} steps: mean {n_sel.mean():.1f}, median {np.median(n_sel):.0f}, "
+          f"p95 {np.percentile(n_sel, 95):.0f}, max {n_sel.max():.0f}")
 
 
 def trace():
