@@ -1644,6 +1644,11 @@ struct PitchArgs {
   float* taps;    // [nw][kPsTapMax]
   int2* yr;       // [n]: the y samples [x, y) of the clip's own span (all written); y is zero outside, unread
   int span;       // 1: the vocoder runs over the workgroup's non-silent span only (0: every frame)
+  // span pairing (NULL: workgroup b takes list positions kPvClips b + cl and scans its rows itself):
+  int2* sp;            // [n]: first / last non-zero sample of list position e (x > y: all zero), ps_span_kernel
+  uint64_t* key;       // [n] list positions, then [groups]: the sort keys (unique: the index is the low bits)
+  int32_t* ord;        // [n]: list positions sorted by (quantised last sample, first sample)
+  int32_t* gord;       // [groups]: groups of kPvClips neighbours of ord, most frames first
 };
 
 __device__ __forceinline__ int ps_i0(const PitchArgs& a, int t, float& alpha) {
@@ -1798,6 +1803,142 @@ __device__ __forceinline__ void pv_scan_span(PvClip& C, const float* xr, int L, 
   }
 }
 
+// the output frames [tb, tl] the vocoder runs for a span of samples [lo, hi] (lo > hi: none), tb a group's
+// first frame (ps_vocoder_kernel, "The groups to run", says why these are enough)
+__device__ __forceinline__ void pv_frames_of(const PitchArgs& a, int lo, int hi, int& tb, int& tl) {
+  const int jmax = (a.l1 + kPsPad - 1) / kPsHop;  // the frame of the last istft sample
+  tb = 0;
+  tl = jmax;
+  float al;
+  if (lo > hi) {
+    tl = -1;  // silent: no frames, y is zero everywhere
+    return;
+  }
+  if (lo > 2 * kPsPad && a.rate < 2.0) {  // (rate < 2: c steps by at most 2 per frame, c = i0(t) after frame t)
+    const int fz = (lo - kPsPad) / kPsHop - 1;  // source frames <= fz are all zero (7 f + 124 < lo)
+    int tg = min(static_cast<int>((fz - 2) / a.rate), a.f_out - 1) & ~(kPvGroup - 1);
+    while (tg > 0 && ps_i0(a, tg - 1, al) + 2 > fz) tg -= kPvGroup;  // sf = c + 2 <= fz at the group's top
+    tb = max(tg, 0);
+  }
+  if (hi < a.L - 1 - 2 * kPsPad) {
+    const int fn = min((hi + kPsPad) / kPsHop, a.f_in - 1);  // the last source frame that can be non-zero
+    int t = max(min(a.f_out - 1, static_cast<int>((fn + 1) / a.rate) + 1), 0);
+    while (t > 0 && ps_i0(a, t, al) > fn) --t;  // the last output frame with i0 <= fn
+    while (t + 1 < a.f_out && ps_i0(a, t + 1, al) <= fn) ++t;
+    tl = min(jmax, t + 36);
+  }
+}
+
+// Span pairing (HBK_PS_PAIR=0: off). A vocoder workgroup runs the union of its clips' spans, and list
+// neighbours are unrelated: on the training clips the union is 0.64 of the window against 0.51 for a
+// clip's own span. So a call orders its clips before the vocoder, on the stream, with fixed grids and no
+// host round trip:
+//  1. ps_span_kernel: one wave per list position scans its row for the first / last non-zero sample (the
+//     scan the vocoder did; from both ends, so the silence is all it reads) and writes the sort key
+//     (1 + last / kPsQuant, first, position): clips that end together and start together are neighbours;
+//  2. ps_rank_kernel: position in sorted order = the number of smaller keys (the keys are unique, so the
+//     order is total and the same on every run: no atomics), ord[rank] = position;
+//  3. ps_group_kernel: each group of kPvClips neighbours of ord gets the key (frames of its union,
+//     descending; group) and ps_rank_kernel orders the groups: the longest workgroups start first.
+// The vocoder's workgroup b takes group gord[b]; y and yr stay indexed by list position.
+constexpr int kPsQuant = 360;  // samples per bucket of the last non-zero sample
+
+__global__ void __launch_bounds__(256) ps_span_kernel(PitchArgs a) {
+  const int lane = threadIdx.x & 63, e = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (e >= a.n) return;  // (wave-uniform)
+  const float* xr = a.x + static_cast<int64_t>(a.idx[e]) * a.x_stride;
+  constexpr int kChunk = 64 * 8;  // samples per step: 8 loads in flight per lane
+  int lo = INT_MAX, hi = -1;
+  for (int p0 = 0; p0 < a.L; p0 += kChunk) {  // forward to the first chunk with a non-zero sample
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int p = p0 + 64 * j + lane;
+      v[j] = p < a.L ? xr[p] : 0.f;
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (v[j] != 0.f) {
+        lo = min(lo, p0 + 64 * j + lane);
+        hi = max(hi, p0 + 64 * j + lane);
+      }
+    if (__any(hi >= 0)) break;
+  }
+  for (int o = 32; o >= 1; o >>= 1) {
+    lo = min(lo, __shfl_xor(lo, o, 64));
+    hi = max(hi, __shfl_xor(hi, o, 64));
+  }
+  if (hi >= 0) {
+    // backward from the end to the first chunk with a non-zero sample (at the latest the chunk of lo)
+    for (int p1 = a.L; p1 > hi + 1; p1 -= kChunk) {
+      float v[8];
+      int h = -1;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int p = p1 - kChunk + 64 * j + lane;
+        v[j] = (p > hi && p < a.L) ? xr[max(p, 0)] : 0.f;
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (v[j] != 0.f) h = max(h, p1 - kChunk + 64 * j + lane);
+      if (__any(h >= 0)) {
+        for (int o = 32; o >= 1; o >>= 1) h = max(h, __shfl_xor(h, o, 64));
+        hi = h;
+        break;
+      }
+    }
+  }
+  if (lane == 0) {
+    a.sp[e] = int2{lo, hi};
+    const uint64_t q = hi < 0 ? 0 : 1 + static_cast<uint64_t>(hi / kPsQuant), f = hi < 0 ? 0 : static_cast<uint64_t>(lo);
+    a.key[e] = (q << 40) | (f << 16) | static_cast<uint64_t>(e);  // hi, lo < 2^24, e < 2^16
+  }
+}
+
+// ord[number of keys below key[i]] = i: 64 keys per workgroup, each of its 16 waves counts over a 16th of
+// the keys, 64 at a time: one load, then each lane's key in turn (v_readlane) against every lane's own
+__global__ void __launch_bounds__(1024) ps_rank_kernel(const uint64_t* __restrict__ key, int n,
+                                                       int32_t* __restrict__ ord) {
+  __shared__ int part[16][64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, i = blockIdx.x * 64 + lane;
+  const uint64_t mine = key[min(i, n - 1)];
+  const int per = (n + 15) / 16, j0 = min(w * per, n), j1 = min(j0 + per, n);
+  int below = 0;
+  for (int jb = j0; jb < j1; jb += 64) {
+    const uint64_t kl = jb + lane < j1 ? key[jb + lane] : ~uint64_t(0);  // (past the range: below no key)
+#pragma unroll
+    for (int q = 0; q < 64; ++q) {
+      const uint32_t hi = __builtin_amdgcn_readlane(static_cast<int>(kl >> 32), q);
+      const uint32_t lo = __builtin_amdgcn_readlane(static_cast<int>(kl), q);
+      below += ((static_cast<uint64_t>(hi) << 32) | lo) < mine;
+    }
+  }
+  part[w][lane] = below;
+  __syncthreads();
+  if (w == 0 && i < n) {
+    int r = 0;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) r += part[q][lane];
+    ord[r] = i;
+  }
+}
+
+// the key of each group of kPvClips neighbours of ord: the groups of its union's frames, descending
+__global__ void __launch_bounds__(256) ps_group_kernel(PitchArgs a, int groups) {
+  const int g = blockIdx.x * 256 + threadIdx.x;
+  if (g >= groups) return;
+  int lo = INT_MAX, hi = -1;
+  for (int c = 0; c < kPvClips; ++c) {
+    const int2 s = a.sp[a.ord[min(kPvClips * g + c, a.n - 1)]];
+    lo = min(lo, s.x);
+    hi = max(hi, s.y);
+  }
+  int tb, tl;
+  pv_frames_of(a, lo, hi, tb, tl);
+  const int steps = tl < tb ? 0 : (tl - tb) / kPvGroup + 1;  // < 2^24 / (7 * 8)
+  a.key[g] = (static_cast<uint64_t>((1 << 24) - steps) << 16) | static_cast<uint64_t>(g);
+}
+
 #ifdef HBK_PHASE_TIMING
 // profiling build: wave 0 of each block sums the s_memtime cycles of the
 // vocoder's phases locally, adds them to g_aug_phase[16 + i] at the end
@@ -1827,8 +1968,10 @@ ps_vocoder_kernel(PitchArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char pv_smem[];
   PvShared& sh = *reinterpret_cast<PvShared*>(pv_smem);
   const int tid = threadIdx.x, cl = tid >> 7, lane = tid & 127;
-  const int e = min(static_cast<int>(blockIdx.x) * kPvClips + cl, a.n - 1);  // padding slots repeat the last clip
-  const bool live = static_cast<int>(blockIdx.x) * kPvClips + cl < a.n;
+  // the workgroup's clips: list positions kPvClips b + cl, or group gord[b] of the span order (a.sp != NULL)
+  const int slot = (a.sp ? a.gord[blockIdx.x] : static_cast<int>(blockIdx.x)) * kPvClips + cl;
+  const int e = a.sp ? a.ord[min(slot, a.n - 1)] : min(slot, a.n - 1);  // padding slots repeat the last clip
+  const bool live = slot < a.n;
   const float* xr = a.x + static_cast<int64_t>(a.idx[e]) * a.x_stride;
   PvClip& C = sh.c[cl];
   // tables
@@ -1841,11 +1984,12 @@ ps_vocoder_kernel(PitchArgs a) {
   }
   if (lane == 0) C.cnt0 = 0;
   if (lane == 0) {
-    C.lo = INT_MAX;
-    C.hi = -1;
+    const int2 s = a.sp ? a.sp[e] : int2{INT_MAX, -1};  // scanned by ps_span_kernel, or below
+    C.lo = s.x;
+    C.hi = s.y;
   }
   __syncthreads();
-  if (a.span) pv_scan_span(C, xr, a.L, lane);
+  if (a.span && !a.sp) pv_scan_span(C, xr, a.L, lane);
   int nz = 0;
   for (int q = lane; q < kPsFft; q += 128) {
     const float v = ps_xp(xr, a.L, q);
@@ -1994,28 +2138,7 @@ ps_vocoder_kernel(PitchArgs a) {
   //    G(t, r) - G(t - 36, r + 2) is zero: the loop ends there, and the resampler reads zeros.
   // A span that comes within 250 samples of either end reaches into the reflect padding: no skip there.
   // frames_of: the output frames [tb, tl] of a span of samples [lo, hi] (lo > hi: none), tb a group's first
-  auto frames_of = [&](int lo, int hi, int& tb, int& tl) {
-    tb = 0;
-    tl = jmax;
-    float al;
-    if (lo > hi) {
-      tl = -1;  // silent: no frames, y is zero everywhere
-      return;
-    }
-    if (lo > 2 * kPsPad && a.rate < 2.0) {  // (rate < 2: c steps by at most 2 per frame, c = i0(t) after frame t)
-      const int fz = (lo - kPsPad) / kPsHop - 1;  // source frames <= fz are all zero (7 f + 124 < lo)
-      int tg = min(static_cast<int>((fz - 2) / a.rate), a.f_out - 1) & ~(kPvGroup - 1);
-      while (tg > 0 && ps_i0(a, tg - 1, al) + 2 > fz) tg -= kPvGroup;  // sf = c + 2 <= fz at the group's top
-      tb = max(tg, 0);
-    }
-    if (hi < a.L - 1 - 2 * kPsPad) {
-      const int fn = min((hi + kPsPad) / kPsHop, a.f_in - 1);  // the last source frame that can be non-zero
-      int t = max(min(a.f_out - 1, static_cast<int>((fn + 1) / a.rate) + 1), 0);
-      while (t > 0 && ps_i0(a, t, al) > fn) --t;  // the last output frame with i0 <= fn
-      while (t + 1 < a.f_out && ps_i0(a, t + 1, al) <= fn) ++t;
-      tl = min(jmax, t + 36);
-    }
-  };
+  auto frames_of = [&](int lo, int hi, int& tb, int& tl) { pv_frames_of(a, lo, hi, tb, tl); };
   int t_beg = 0, t_last = jmax;
   {
     // the clip's own frames give the y range its resampler reads (the rest of y is zero, whatever a
@@ -2896,13 +3019,17 @@ static int64_t ps_bytes(const hbk::PitchArgs& a, int64_t n, int64_t* off) {
   off[0] = off[1] = off[2] = off[3] = 0;           // y
   off[4] = up(n * a.l1 * 4);                       // taps
   off[5] = off[4] + up(int64_t(kPsPhaseMax) * kPsTapMax * 4);  // the clips' computed y ranges
-  return off[5] + up(n * int64_t(sizeof(int2)));
+  off[6] = off[5] + up(n * int64_t(sizeof(int2)));             // span pairing: the clips' spans,
+  off[7] = off[6] + up(n * int64_t(sizeof(int2)));             // the sort keys,
+  off[8] = off[7] + up(n * int64_t(sizeof(uint64_t)));         // the clips' order
+  off[9] = off[8] + up(n * int64_t(sizeof(int32_t)));          // and the groups'
+  return off[9] + up(n * int64_t(sizeof(int32_t)));
 }
 
 int64_t hbk_pitch_shift_workspace_size(int64_t n, int64_t T, int32_t sample_rate, int32_t num, int32_t den) {
   hbk::PitchArgs a{};
   if (n <= 0 || ps_geometry(T, sample_rate, num, den, a) != HBK_OK) return 0;
-  int64_t off[6];
+  int64_t off[10];
   return ps_bytes(a, n, off);
 }
 
@@ -2918,7 +3045,7 @@ int hbk_pitch_shift(const float* x, int64_t x_stride, int64_t n, const int32_t* 
   const int rc = ps_geometry(T, sample_rate, num, den, a);
   if (rc != HBK_OK) return rc;
   if (x_stride < T || out_stride < T) return arg_error("stride < T");
-  int64_t off[6];
+  int64_t off[10];
   if (workspace_bytes < ps_bytes(a, n, off)) return arg_error("workspace too small (hbk_pitch_shift_workspace_size)");
   unsigned char* w = static_cast<unsigned char*>(workspace);
   a.x = x;
@@ -2935,9 +3062,28 @@ int hbk_pitch_shift(const float* x, int64_t x_stride, int64_t n, const int32_t* 
     return s && s[0] == '0';
   }();
   a.span = span_off ? 0 : 1;
+  // HBK_PS_PAIR=0: workgroups take list neighbours and scan their own rows (A/B; read per call, so one
+  // process can compare both). Without spans there is nothing to pair by.
+  const char* pair_env = getenv("HBK_PS_PAIR");
+  const bool pair = a.span && !(pair_env && pair_env[0] == '0');
   hipStream_t st = as_stream(stream);
   hipLaunchKernelGGL(ps_taps_kernel, dim3(unsigned((a.nw * kPsTapMax + 255) / 256)), dim3(256), 0, st, a);
   HBK_LAUNCH_CHECK("ps_taps_kernel");
+  const int groups = static_cast<int>((n + kPvClips - 1) / kPvClips);
+  if (pair) {
+    a.sp = reinterpret_cast<int2*>(w + off[6]);
+    a.key = reinterpret_cast<uint64_t*>(w + off[7]);
+    a.ord = reinterpret_cast<int32_t*>(w + off[8]);
+    a.gord = reinterpret_cast<int32_t*>(w + off[9]);
+    hipLaunchKernelGGL(ps_span_kernel, dim3(unsigned((n + 3) / 4)), dim3(256), 0, st, a);
+    HBK_LAUNCH_CHECK("ps_span_kernel");
+    hipLaunchKernelGGL(ps_rank_kernel, dim3(unsigned((n + 63) / 64)), dim3(1024), 0, st, static_cast<const uint64_t*>(a.key), a.n, a.ord);
+    HBK_LAUNCH_CHECK("ps_rank_kernel");
+    hipLaunchKernelGGL(ps_group_kernel, dim3(unsigned((groups + 255) / 256)), dim3(256), 0, st, a, groups);
+    HBK_LAUNCH_CHECK("ps_group_kernel");
+    hipLaunchKernelGGL(ps_rank_kernel, dim3(unsigned((groups + 63) / 64)), dim3(1024), 0, st, static_cast<const uint64_t*>(a.key), groups, a.gord);
+    HBK_LAUNCH_CHECK("ps_rank_kernel");
+  }
   static bool lds_set = false;  // > 64 KB of dynamic LDS needs the opt-in (per process, idempotent)
   if (!lds_set) {
     HBK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ps_vocoder_kernel),

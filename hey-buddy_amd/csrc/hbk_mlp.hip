@@ -773,6 +773,14 @@ int hbk_mlp_eval_count(const hbk_mlp_plan* p, const float* params, const void* p
                         as_stream(stream));
 }
 
+int hbk_mlp_eval_laps(int64_t rows, int64_t n_pool, int32_t pool_is_f16, int32_t has_idx, int64_t* parts) {
+  using namespace hbk;
+  if (!parts) return arg_error("NULL pointer");
+  if (rows < 0 || n_pool <= 0) return arg_error("rows / n_pool out of range");
+  mlp_eval_lap_plan(rows, n_pool, pool_is_f16 != 0, has_idx != 0, parts);
+  return HBK_OK;
+}
+
 int hbk_mlp_eval_count_multi(const hbk_mlp_plan* p, const float* params, int32_t n_pools,
                              const void* const* pools, int32_t pools_are_f16, const int64_t* n_pool,
                              const int64_t* rows, const int64_t* row_offsets, const int32_t* labels,

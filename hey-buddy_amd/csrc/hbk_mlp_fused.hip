@@ -2586,6 +2586,7 @@ struct KvArgs {
   uint64_t seg_seed[kKvMaxSeg];
   float* seg_counts[kKvMaxSeg];
   int seg_label[kKvMaxSeg];
+  int lap_tiles;  // the lap form (kLap > 0): workgroups per lap set, ceil(n_pool / 128); rows = whole sets
 };
 
 __global__ void __launch_bounds__(256) kv_prep_kernel(const float* __restrict__ P, int64_t w0, int64_t g_in,
@@ -2653,8 +2654,18 @@ __device__ __forceinline__ int kv_swz(int n) { return (n >> 1) & 7; }
 constexpr int kNetWLd = 104, kAld = 100;  // LDS row strides: weight halves (K <= 96), activation floats
 // W: waves per workgroup, 8 (f16 rows: two 16-row tiles per wave) or 16 (one tile per wave:
 // twice the waves per CU to hide the stream's latency, at most 128 VGPRs each)
-template <bool kF16, int NG, int W>
+// kLap = 2, the lap form (f16 pools read in order, 8 waves): a pass that reads its pool several times
+// over evaluates every pool row once per lap, and only the dropout mask (a hash of the row's index in the
+// pass) differs between the laps. So a wave's two tiles are two laps of the SAME 16 pool rows: one load
+// of the raw rows per chunk, masked and converted once per lap: 1.5 + 3 KB per row evaluation against
+// 3 + 3 KB. The launch covers whole lap sets: set q is the row evaluations [2 q n_pool, 2 (q + 1) n_pool)
+// of the launch, its workgroup t the pool rows (r0 + 16 W t ..) % n_pool (a wrap inside a tile is per
+// lane; the last tile's rows past n_pool are dead). Every row evaluation keeps its values, chunk order
+// and MFMA sequence, so prob and the counts are those of the plain form, bit for bit. (Four laps per wave
+// need 128 accumulator registers of the 256: hipcc spills inside the chunk loop)
+template <bool kF16, int NG, int W, int kLap = 0>
 __global__ void __launch_bounds__(64 * W) kv_gemm_kernel(KvArgs a0) {
+  static_assert(kLap == 0 || (kF16 && W == 8 && kLap == 2), "the lap form: f16 rows, 8 waves of two laps");
   // this workgroup's pool (segment): its fields replace the single-pool ones (uniform)
   KvArgs a = a0;
   int blk = static_cast<int>(blockIdx.x);
@@ -2678,7 +2689,8 @@ __global__ void __launch_bounds__(64 * W) kv_gemm_kernel(KvArgs a0) {
   // statistics reuse buffer 0 after it); network phase: a stage's weight planes
   // at 0, the waves' activation tiles after them, two counters last.
   constexpr int kWBuf = 3;  // W' ring: chunk c + 2's DMA is issued during chunk c (kWBuf - 1 == 2 assumed below)
-  constexpr int kRT = (kF16 && W == 8) ? 2 : 1;  // 16-row tiles per wave (f32 rows: one, for the split's registers)
+  constexpr int kRT = kLap ? kLap : (kF16 && W == 8) ? 2 : 1;  // 16-row tiles per wave (f32 rows: one, for the split's registers)
+  constexpr int kAT = kLap ? 1 : kRT;         // of them loaded: the laps share one tile of raw rows
   constexpr int kThr = 64 * W;
   constexpr int kGemmBytes = kWBuf * 2 * kH2 * kKvKC * 2;
   constexpr int kWsBytes = 2 * kH2 * kNetWLd * 2;
@@ -2695,14 +2707,36 @@ __global__ void __launch_bounds__(64 * W) kv_gemm_kernel(KvArgs a0) {
   constexpr int kDepth = kF16 ? HBK_KV_DEPTH : 2;  // A chunks in flight (this one + kDepth - 1 ahead)
   constexpr int kBGroup = kDepth > 2 ? 2 : 4;       // column tiles whose B fragments may be in flight together
   constexpr int kU = kF16 ? 1 : 2;  // 16-B loads per 8 elements
-  constexpr int kALoads = kRT * 2 * kU;  // per chunk
+  constexpr int kALoads = kAT * 2 * kU;  // per chunk
   constexpr int kTile = W * 16 * kRT;
   constexpr int kDma = 32 / W;  // W' DMA instructions per wave and chunk (2 planes x 128 rows of 128 B)
   static_assert(kALoads * (kDepth - 1) + kDma < 16, "the counted waits use vmcnt's low field");
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, m = lane & 15, kq = lane >> 4;
   const int64_t tile0 = int64_t(blk) * kTile;
-  const char* rp[kRT];
+  // the lap form: the set's first row evaluation, and the wave's first row of the set's lap 0
+  const int64_t lap_s = kLap ? int64_t(blk / max(a.lap_tiles, 1)) * kLap * a.n_pool : 0;
+  const int64_t lap_b = kLap ? int64_t(blk % max(a.lap_tiles, 1)) * (16 * W) + 16 * wave : 0;
+  // row j of the wave's tile rt: its row evaluation in the launch, and whether there is one
+  auto row_of = [&](int rt, int j, bool& live) -> int64_t {
+    if constexpr (kLap > 0) {
+      const int64_t r = lap_s + rt * a.n_pool + lap_b + j;
+      live = lap_b + j < a.n_pool && r < a.rows;
+      return r;
+    } else {
+      const int64_t r = tile0 + 16 * kRT * wave + 16 * rt + j;
+      live = r < a.rows;
+      return r;
+    }
+  };
+  const char* rp[kAT];
   uint32_t rid[kRT];
+  if constexpr (kLap > 0) {
+    const int64_t b = min(lap_b + m, a.n_pool - 1);  // (dead rows repeat the pool's last one)
+    const int64_t pr = min(max((a.r0 + b) % a.n_pool, int64_t(0)), a.n_pool - 1);  // lap_s is whole laps
+    rp[0] = static_cast<const char*>(a.pool) + pr * kD * 2;
+#pragma unroll
+    for (int rt = 0; rt < kRT; ++rt) rid[rt] = static_cast<uint32_t>(a.r0 + lap_s + rt * a.n_pool + b);
+  } else {
 #pragma unroll
   for (int rt = 0; rt < kRT; ++rt) {
     const int64_t r = min(tile0 + 16 * kRT * wave + 16 * rt + m, a.rows - 1);
@@ -2711,14 +2745,15 @@ __global__ void __launch_bounds__(64 * W) kv_gemm_kernel(KvArgs a0) {
     rp[rt] = static_cast<const char*>(a.pool) + pr * kD * (kF16 ? 2 : 4);
     rid[rt] = static_cast<uint32_t>(a.r0 + r);
   }
+  }
   const uint64_t seed = a.seed;
   const uint32_t s0 = static_cast<uint32_t>(seed), s1 = static_cast<uint32_t>(seed >> 32) * 0x27D4EB2Fu;
   const uint32_t thr = static_cast<uint32_t>(a.drop_p * 65536.f + 0.5f);
   const float keep = a.drop_p > 0.f ? 1.f / (1.f - a.drop_p) : 1.f;
-  uint4 ar[kDepth][kRT][2][kU];
+  uint4 ar[kDepth][kAT][2][kU];
   auto load_rows = [&](int c, int slot) {
 #pragma unroll
-    for (int rt = 0; rt < kRT; ++rt)
+    for (int rt = 0; rt < kAT; ++rt)
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb) {
         const int k = kKvKC * c + 32 * kb + 8 * kq;
@@ -2776,12 +2811,12 @@ __global__ void __launch_bounds__(64 * W) kv_gemm_kernel(KvArgs a0) {
       for (int rt = 0; rt < kRT; ++rt) {
         float v[8];
         if (kF16) {
-          const h8 hv = __builtin_bit_cast(h8, ar[slot][rt][kb][0]);
+          const h8 hv = __builtin_bit_cast(h8, ar[slot][kLap ? 0 : rt][kb][0]);
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] = static_cast<float>(hv[e]);
         } else {
 #pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] = __builtin_bit_cast(float, (&ar[slot][rt][kb][e >> 2].x)[e & 3]);
+          for (int e = 0; e < 8; ++e) v[e] = __builtin_bit_cast(float, (&ar[slot][kLap ? 0 : rt][kb][e >> 2].x)[e & 3]);
         }
         if (!(HBK_KV_ABLATE & 2) && a.drop_p > 0.f) {  // nn.Dropout's mask (the 1 / (1 - p) scale is applied after the GEMM)
           const uint32_t base = rid[rt] * (kD / 2) + ((kKvKC * c + 32 * kb + 8 * kq) >> 1);
@@ -3056,8 +3091,9 @@ __global__ void __launch_bounds__(64 * W) kv_gemm_kernel(KvArgs a0) {
       z += dpp_f<0xB1>(z);  // quad_perm: lanes ^ 1, ^ 2 hold the row's other columns
       z += dpp_f<0x4E>(z);
       z += bz;
-      const int64_t row = tile0 + 16 * kRT * wave + 16 * rt + r;
-      const bool live = row < a.rows && (lane & 3) == 0;
+      bool live;
+      const int64_t row = row_of(rt, r, live);
+      live = live && (lane & 3) == 0;
       const float p = sigm_fast(z);
       if (live && a.prob) a.prob[row] = p;
       ge += __popcll(__ballot(live && p >= a.act_thr));
@@ -3761,6 +3797,19 @@ int mlp_eval_prepare(const hbk_mlp_plan& p, const float* params, float* ws, hipS
   return HBK_OK;
 }
 
+// How a single-pool pass of `rows` row evaluations is launched: part[0] rows in the lap form (whole sets
+// of two laps, so no set carries a dead lap), part[1] in the plain form. Laps are for f16 pools read in
+// order that the pass covers at least twice. HBK_EVAL_LAPS=0 (read per call, so one process can compare)
+// restores the plain form everywhere.
+void mlp_eval_lap_plan(int64_t rows, int64_t n_pool, bool f16, bool has_idx, int64_t part[2]) {
+  part[0] = 0;
+  part[1] = rows;
+  const char* e = getenv("HBK_EVAL_LAPS");
+  if ((e && e[0] == '0') || !f16 || has_idx || n_pool <= 0 || rows <= 0) return;
+  part[0] = rows / (2 * n_pool) * (2 * n_pool);
+  part[1] = rows - part[0];
+}
+
 // One kv_gemm_kernel launch over nseg pools of one dtype (nseg = 1: the single-pool fields,
 // which also allow idx / prob; nseg > 1: the segment table, workgroups in pool order).
 static int mlp_eval_launch(const hbk_mlp_plan& p, const float* params, bool f16, const EvalSeg* seg, int nseg,
@@ -3819,6 +3868,27 @@ static int mlp_eval_launch(const hbk_mlp_plan& p, const float* params, bool f16,
       tiles += (seg[i].rows + tile - 1) / tile;
     }
     ka.seg_tile0[nseg] = static_cast<int>(tiles);
+  }
+  // the lap form first, over the pass's whole lap sets; what is left goes to the plain form
+  if (nseg == 1) {
+    int64_t part[2];
+    mlp_eval_lap_plan(seg[0].rows, seg[0].n_pool, f16, idx != nullptr, part);
+    if (part[0] > 0) {
+      ka.lap_tiles = static_cast<int>((seg[0].n_pool + 127) / 128);
+      ka.rows = part[0];
+      const dim3 lgrid(static_cast<unsigned>(part[0] / (2 * seg[0].n_pool) * ka.lap_tiles));
+      auto llaunch = [&](auto kern) { hipLaunchKernelGGL(kern, lgrid, dim3(512), 0, s, ka); };
+      if (NG == 2) llaunch(kv_gemm_kernel<true, 2, 8, 2>);
+      else if (NG == 3) llaunch(kv_gemm_kernel<true, 3, 8, 2>);
+      else llaunch(kv_gemm_kernel<true, 4, 8, 2>);
+      HBK_LAUNCH_CHECK("kv_gemm_kernel (laps)");
+      ka.r0 += part[0];
+      if (ka.prob) ka.prob += part[0];
+      ka.lap_tiles = 0;
+      ka.rows = part[1];
+      if (part[1] == 0) return HBK_OK;
+      tiles = (part[1] + tile - 1) / tile;
+    }
   }
   const dim3 grid(static_cast<unsigned>(tiles));
   auto launch = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(64 * waves), 0, s, ka); };

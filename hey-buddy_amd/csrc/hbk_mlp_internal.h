@@ -73,6 +73,8 @@ int mlp_eval_prepare(const hbk_mlp_plan& p, const float* params, float* ws, hipS
 int mlp_eval_count(const hbk_mlp_plan& p, const float* params, const void* pool, bool f16, int64_t n_pool,
                    const int32_t* idx, int64_t rows, int64_t r0, int label, float act_thr, float drop_p,
                    uint64_t seed, float* counts, float* prob, float* ws, hipStream_t s);
+// the rows mlp_eval_count evaluates in the lap form (two laps of the pool together) and in the plain form
+void mlp_eval_lap_plan(int64_t rows, int64_t n_pool, bool f16, bool has_idx, int64_t part[2]);
 // one pool of an evaluation launch (mlp_eval_count_multi: several pools of one dtype in one launch)
 struct EvalSeg {
   const void* pool;

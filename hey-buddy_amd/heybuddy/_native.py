@@ -123,6 +123,8 @@ _PROTOS = {
     "hbk_mlp_eval_count": (_c_int, [_vp, _vp, _vp, ctypes.c_int32, _c_int64, _vp, _c_int64, _c_int64,
                                     ctypes.c_int32, _c_float, _c_float, ctypes.c_uint64, _vp, _vp, _vp, _c_int64,
                                     _vp]),
+    "hbk_mlp_eval_laps": (_c_int, [_c_int64, _c_int64, ctypes.c_int32, ctypes.c_int32,
+                                   ctypes.POINTER(_c_int64)]),
     "hbk_mlp_eval_finish": (_c_int, [_vp, _vp, ctypes.POINTER(ctypes.c_double), _c_float, _c_float, _vp,
                                      _c_int64, _c_int64, _vp, _vp]),
 }

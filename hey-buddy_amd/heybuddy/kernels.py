@@ -573,6 +573,16 @@ class MlpPlan:
                                       float(activation_threshold), float(dropout_p), _u64_to_i64(seed), counts, prob,
                                       ws, self.id)
 
+    @staticmethod
+    def eval_laps(rows: int, n_pool: int, f16: bool = True, has_idx: bool = False) -> tuple:
+        """How eval_count launches such a pass (hbk_mlp_eval_laps): the rows it
+        evaluates (two laps of the pool at a time, in the plain form).
+        HBK_EVAL_LAPS=0 in the environment turns the lap form off."""
+        parts = (ctypes.c_int64 * 2)()
+        check(lib().hbk_mlp_eval_laps(int(rows), int(n_pool), int(bool(f16)), int(bool(has_idx)), parts),
+              "hbk_mlp_eval_laps")
+        return tuple(int(v) for v in parts)
+
     def eval_count_multi(self, params: torch.Tensor, parts, counts: torch.Tensor, ws: torch.Tensor,
                          activation_threshold: float = 0.5, dropout_p: float = 0.0) -> None:
         """eval_count for up to 4 pools of one dtype in ONE launch (hbk_mlp_eval_count_multi):

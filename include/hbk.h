@@ -352,6 +352,12 @@ int hbk_mlp_eval_count(const hbk_mlp_plan* plan, const float* params, const void
                        int64_t n_pool, const int32_t* idx, int64_t rows, int64_t row_offset, int32_t label,
                        float activation_threshold, float dropout_p, uint64_t seed, float* counts, float* prob,
                        void* workspace, int64_t workspace_bytes, void* stream);
+/* How hbk_mlp_eval_count launches such a pass (a query: nothing runs). A pass that covers an f16 pool
+ * read in order (idx == NULL) several times over evaluates each pool row once per lap with another
+ * dropout mask, so two laps of a row share its load: parts[0] rows are evaluated two laps at a time
+ * (whole sets of two laps), parts[1] in the plain form; every result is the plain form's, bit for
+ * bit. HBK_EVAL_LAPS=0 in the environment (read per call) turns the lap form off. parts: int64[2]. */
+int hbk_mlp_eval_laps(int64_t rows, int64_t n_pool, int32_t pool_is_f16, int32_t has_idx, int64_t* parts);
 /* hbk_mlp_eval_count for n_pools (<= 4) pools of one dtype in ONE launch: pool i's rows
  * r = 0 .. rows[i]-1 are pool rows (row_offsets[i] + r) % n_pool[i], labelled labels[i], counted
  * into counts[i] with dropout seed seeds[i], each exactly as its own hbk_mlp_eval_count (no idx, no
