@@ -5,17 +5,21 @@
 // Replaces, per optimisation step of WakeWordTrainer.train_epoch
 // (trainer.py:380-494), the reference's forward (wakeword.py:334-348), the
 // high-loss filter and weighted BCE (:407-445), autograd backward and
-// torch.optim.Adam (:45, :460-462), with FOUR launches and no host sync:
+// torch.optim.Adam (:45, :460-462), with four or five launches and no host sync.
+// There are two steps; plan_step (hbk_mlp_plan.h) takes v2 for large batches on a
+// narrow (CU-masked) stream, the headline's train stream, and v1 otherwise:
 //
-//   k1a        gather the batch rows from the embedding pools by index (f32
-//              or f16 pool), input dropout, LayerNorm(1536) -> xhat^T in HBM.
-//              It needs no weights, so step s + 1's k1a runs as extra
-//              workgroups of step s's k2 launch, two row tiles each (k2 fills
-//              35 of 256 CUs at B = 1100, two workgroups per CU) and is off
-//              the critical path; a standalone launch covers the first step
-//              and steps without a known successor
-//   k1b        the input GEMM HG0 = (xhat g + b) W_hg0^T as split-K partial
-//              slabs (row tiles of 16 x K-chunks: ~576 workgroups at B = 1100)
+//   rows       v1, k1a: gather the batch rows from the embedding pools by index
+//              (f32 or f16 pool), input dropout, LayerNorm(1536) -> xhat^T in HBM.
+//              v2, k1s: the rows' LayerNorm statistics, addresses and dropout
+//              mask only (no xhat^T: its consumers read the pool rows).
+//              Neither needs weights, so step s + 1's rows run as extra
+//              workgroups of step s's k2 launch and are off the critical path; a
+//              standalone launch covers the first step and steps without a known
+//              successor
+//   input GEMM HG0 = (xhat g + b) W_hg0^T as split-K partial slabs. v1, k1b: from
+//              xhat^T, 64 rows x one K chunk per workgroup. v2, k1c: from the pool
+//              rows, 16 RT rows x one K chunk, geometry by a per-CU byte model
 //   k2_rows    per 16-row tile, the whole rest of the network in LDS:
 //              sum of the HG0 partials + bias, SiLU gate, every gated MLP and
 //              LayerNorm forward, sigmoid, the high-loss filter, weighted BCE
@@ -23,17 +27,29 @@
 //              bias and LayerNorm(96) gradients as per-tile column sums
 //              (float atomics); activations for the weight gradients to HBM.
 //              A tile none of whose rows the filter kept ends after the loss
-//              stage (zero gradient rows and maxima written), and the v2
-//              weight-gradient kernel k3s walks the other tiles only
-//   k3_wgrad   every weight gradient dW = dY^T X as split-K MFMA tiles with
-//              atomic accumulation into the gradient bucket; the input layer's
-//              tiles also produce the norm_in gamma/beta gradients from the
-//              same product (dW_hg0 = g o (dHG0^T xhat) + beta (x) colsum dHG0,
+//              stage (zero gradient rows and maxima written)
+//   weight     every weight gradient dW = dY^T X as split-K MFMA tiles, one
+//   gradients  partial slab per batch split (plain stores); the input layer's
+//              tiles also produce the norm_in gamma / beta gradients from the same
+//              product (dW_hg0 = g o (dHG0^T xhat) + beta (x) colsum dHG0,
 //              dgamma = sum_j W o (dHG0^T xhat), dbeta = colsum(dHG0) W_hg0;
-//              colsum dHG0 itself = the hidden/gate bias gradient, from k2)
-//   [RCCL all-reduce of the bucket between k3 and k4 when data-parallel]
-//   k4_update  the < 128-sample accumulation gate, Adam, and zeroing of the
-//              bucket for the next step
+//              colsum dHG0 itself = the hidden/gate bias gradient, from k2).
+//              v1, k3_wgrad: 128 x 32 tiles over xhat^T. v2, k3s: 128 x 256 / 128
+//              tiles, the input layer's X recomputed from the pool rows, walking
+//              only the row tiles that hold a row the filter kept
+//   k3_fold    the slabs added into the bucket -- unless the update that follows
+//              gets this workspace (HBK_STEP_DEFER_PARTIALS: k4 sums them)
+//   [RCCL all-reduce of the bucket between the fold and k4 when data-parallel]
+//   k4_update  the < 128-sample accumulation gate, Adam, zeroing of the bucket for
+//              the next step, and the weight cache (k0_wsplit writes it when the
+//              previous step's k4 did not)
+//
+// Where the rest lives: hbk_mlp_plan.h, the step's planning as pure host C++ (the
+// variant, every kernel's geometry, the job tables' shapes, the workspace layout,
+// the environment knobs); hbk_mlp_dev.h, the device helpers shared with
+// hbk_mlp_eval.hip, the evaluation passes. This file keeps every kernel that uses
+// the trace (HBK_MT*) and bounds (BCK) macros: their __device__ globals belong to
+// one translation unit, and tools/probe_bounds.py reports lines of this file.
 //
 // GEMMs are split-f16 products (hi*hi + hi*lo + lo*hi of f16 hi / lo parts,
 // f32 accumulation, operands power-of-two scaled into the f16 range): ~22-bit
@@ -56,90 +72,14 @@
 #include <cstdio>
 
 #include "hbk_common.h"
+#include "hbk_mlp_dev.h"
 #include "hbk_mlp_internal.h"
+#include "hbk_mlp_plan.h"
 
 namespace hbk {
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-
-constexpr int kD = 1536, kL = 96, kH = 64, kH2 = 128;
-constexpr int kR = 16;            // rows per tile = MFMA M
-constexpr int kMaxG = 4;          // gated MLPs held by k2 (n_layers <= 2: the LDS budget)
 constexpr int kStats = 8;
-constexpr float kLnEps = 1e-5f;
-constexpr int kLd = 132;          // LDS row stride of [16][<=128] activation tiles
-constexpr int kChunkMax = 384;    // k1 K-chunk
-
-__device__ __forceinline__ f4 mma(float a, float b, f4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-// wave sum through DPP: quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror,
-// row_mirror leave each 16-lane row's sum in all of its lanes (rsum16); the
-// four rows are then added from readlane (a bpermute-based __shfl_xor chain
-// costs an LDS round trip per step)
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float x) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), CTRL, 0xF, 0xF, false));
-}
-__device__ __forceinline__ float rsum16(float v) {
-  v += dpp_f<0xB1>(v);
-  v += dpp_f<0x4E>(v);
-  v += dpp_f<0x141>(v);
-  v += dpp_f<0x140>(v);
-  return v;
-}
-__device__ __forceinline__ float wsum(float v) {
-  v = rsum16(v);
-  const int b = __builtin_bit_cast(int, v);
-  return (__builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 0)) +
-          __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 16))) +
-         (__builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 32)) +
-          __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 48)));
-}
-__device__ __forceinline__ float wmax(float v) {
-  v = fmaxf(v, dpp_f<0xB1>(v));
-  v = fmaxf(v, dpp_f<0x4E>(v));
-  v = fmaxf(v, dpp_f<0x141>(v));
-  v = fmaxf(v, dpp_f<0x140>(v));
-  const int b = __builtin_bit_cast(int, v);
-  return fmaxf(fmaxf(__builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 0)),
-                     __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 16))),
-               fmaxf(__builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 32)),
-                     __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 48))));
-}
-__device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
-// The gates (train step and evaluation) and the evaluation's output: the hardware
-// exp2 and reciprocal (1 ulp each) instead of expf's range reduction and the IEEE
-// division sequence (~20 VALU instructions per sigmoid, on k2's dependent
-// stages); values move by ~1e-7 relative (the tests' tolerances are >= 1e-5, and
-// their counts allow predictions that near the threshold). The train step's loss
-// stage keeps sigm (its high-loss filter compares p with thresholds).
-__device__ __forceinline__ float sigm_fast(float x) {
-  return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.44269504088896341f * x));
-}
-
-// Barrier of a loop with global->LDS DMA in flight (its waits counted by hand
-// before it): a fenced barrier would wait vmcnt(0), as the DMA writes LDS. The
-// empty asm statements keep the compiler from moving memory accesses across.
-__device__ __forceinline__ void dma_barrier() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-// Workgroup barrier for LDS traffic only (the evaluation network's stages):
-// the release / acquire fences are restricted to the local address space, so
-// the barrier waits for the wave's LDS operations (lgkmcnt) but not for the
-// next stage's weight loads in flight (a plain __syncthreads() waits vmcnt(0)
-// too). Its waves hand nothing to each other through global memory. (In the
-// train step's k2 the same change measured no difference: 36.89 vs 36.89 us.)
-__device__ __forceinline__ void lds_barrier() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
 
 #ifdef HBK_TRACE
 // Tracing build only (lib/libhbk_trace.so, tools/probe_mlp.py): lane 0 of every
@@ -253,20 +193,6 @@ struct K1bArgs {
   float* stats;       // bucket tail, zeroed here (k2 accumulates into it); may be NULL
 };
 
-// 32-bit counter hash for the input dropout mask (murmur3's finaliser over
-// the element-pair index mixed with the step's 64-bit seed): one hash gives
-// the 16-bit uniforms of elements 2 i and 2 i + 1 (p resolved to 2^-16).
-__device__ __forceinline__ uint32_t drop_hash(uint32_t s0, uint32_t s1, uint32_t i) {
-  uint32_t h = i * 0x9E3779B1u + s0;
-  h ^= s1;
-  h ^= h >> 16;
-  h *= 0x85EBCA6Bu;
-  h ^= h >> 13;
-  h *= 0xC2B2AE35u;
-  h ^= h >> 16;
-  return h;
-}
-
 // k1a: one 16-row tile, full width. Every loop is unrolled and every global
 // load unconditional (a row outside its pool reads a valid fallback row and is
 // zeroed afterwards), so the vmcnt waits are exact and a wave's four rows are
@@ -277,9 +203,6 @@ __device__ __forceinline__ uint32_t drop_hash(uint32_t s0, uint32_t s1, uint32_t
 // [512 t, 512 t + 512), so xhat^T is written in three 512-column slabs staged
 // through LDS (slab: [16][516] floats) as 64-B column runs.
 constexpr int kSlabLd = 516;
-constexpr int kPreTiles = 2;    // k1a row tiles per prefetch workgroup of k2 (v1)
-constexpr int kPreTiles2 = 3;   // k1s (v2: statistics and mask only) row tiles per prefetch workgroup (2: 84.0, 3: 83.6, 4: 86.0 us per step)
-constexpr int kMaskW = kD / 32;  // mask words per row
 // kV2: the row statistics and dropout mask (rinfo, mask) instead of xhat^T; slab is then
 // >= 4 waves x 4 rows x 1536 bytes of LDS scratch (the mask's byte image)
 template <bool kIdx, bool kV2 = false>
@@ -448,43 +371,6 @@ __global__ void __launch_bounds__(256) k1s_kernel(K1aArgs a, int next) {
   k1a_tile<kIdx, true>(a, blockIdx.x, step, nullptr, slab, a.parity ^ next);
 }
 
-// Split-f16 products on v_mfma_f32_16x16x32_f16: v = hi + lo with hi = f16(v)
-// and lo = f16(v - hi) (v - hi is exact in f32), so
-// a . b ~ hi_a hi_b + hi_a lo_b + lo_a hi_b: three f16 MFMAs (16 cycles each
-// per 16x16x32) for the 8 f32 MFMAs (32 cycles each) of the same 32-deep
-// product. hi is rounded to nearest (v_cvt_pk_f16_f32), so |lo| <= 2^-11 |x|
-// with either sign and the dropped lo_a lo_b is an unbiased ~2^-22 relative
-// term (a round-toward-zero hi makes it up to 2^-20 and one-signed, a bias that
-// survives long sums). lo = x - hi is exact in f32 before its rounding to f16.
-// Plain vector code (cvt_pk, two cvt back, pk_fma, cvt_pk per pair): the
-// compiler sees every operand and places the wait states itself. Callers keep
-// |x| < 2^15.
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-typedef float f2v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void split_pair(float a, float b, uint32_t& hi, uint32_t& lo) {
-  const h2v h = __builtin_convertvector(f2v{a, b}, h2v);
-  const f2v r = f2v{a, b} - __builtin_convertvector(h, f2v);
-  hi = __builtin_bit_cast(uint32_t, h);
-  lo = __builtin_bit_cast(uint32_t, __builtin_convertvector(r, h2v));
-}
-// 8 floats (two f4) -> hi / lo h8
-__device__ __forceinline__ void split8(const f4& x0, const f4& x1, h8& hi, h8& lo) {
-  uint32_t h[4], l[4];
-  split_pair(x0[0], x0[1], h[0], l[0]);
-  split_pair(x0[2], x0[3], h[1], l[1]);
-  split_pair(x1[0], x1[1], h[2], l[2]);
-  split_pair(x1[2], x1[3], h[3], l[3]);
-  typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-  hi = __builtin_bit_cast(h8, u4{h[0], h[1], h[2], h[3]});
-  lo = __builtin_bit_cast(h8, u4{l[0], l[1], l[2], l[3]});
-}
-__device__ __forceinline__ f4 mma3(const h8& ah, const h8& al, const h8& bh, const h8& bl, f4 c) {
-  c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, c, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, c, 0, 0, 0);
-}
-
 // k1b: HG0 partials for 64 rows x one K-chunk per workgroup (4 MFMA row tiles
 // share each W fragment: W is read from L2 ceil(B / 64) times per step, not
 // ceil(B / 16)). Grid: the KS chunks of one 64-row block run on ONE XCD
@@ -493,7 +379,6 @@ __device__ __forceinline__ f4 mma3(const h8& ah, const h8& al, const h8& bh, con
 // xhat^T tile, norm_in's gamma / beta, the chunk's W_hg0 fragments), then the
 // unrolled split-f16 chain. W is scaled by 16 before the split (keeps lo of
 // |W| ~ 1e-2 in f16's normal range); the sums are scaled back exactly.
-constexpr int kRB = 64;
 template <int KS>
 __global__ void __launch_bounds__(256) k1b_kernel(K1bArgs a) {
   constexpr int kChunk = kD / KS, kN32 = kChunk / 32, kXl = kChunk / 16;  // xhat^T f4 loads per thread
@@ -612,10 +497,6 @@ struct K1cArgs {
   float* hg_part;         // [KS][B][128]
   float* stats;           // bucket tail, zeroed here (k2 accumulates into it); may be NULL
 };
-template <int KC>
-constexpr int k1c_rt_max() {
-  return 16 * (KC + 16) * 4 * 9 <= 150 * 1024 ? 9 : (150 * 1024) / (16 * (KC + 16) * 4);
-}
 // A load through a pointer the compiler cannot trace to a kernel argument (a row address
 // read from memory) is emitted as a FLAT load, which counts in both vmcnt and lgkmcnt and
 // is waited for with vmcnt(0) lgkmcnt(0) -- it serialised k3s's gathers. ldg: the same
@@ -765,112 +646,14 @@ __global__ void __launch_bounds__(512) k1c_kernel(K1cArgs a) {
 // scales A by a power of two into [2^14, 2^15) before the split; W is scaled by
 // 16 (as in k1b). The sums are scaled back exactly. Gradients (multiples of dz)
 // can be arbitrarily small and activations large: neither leaves f16's range.
-// Weight fragments come pre-split from the step's weight cache (WSplit below:
+// Weight fragments (WFrag / load_wf, hbk_mlp_dev.h, with the A fragments and the
+// GEMM chains) come pre-split from the step's weight cache (WSplit, there too:
 // f16 hi / lo planes of 16 W, written by k4 with every update): T tiles of a
 // [N][K] matrix (k contiguous), lane (n, kq) of block i holding k = 32 i + 8 kq
 // .. + 7 of row n. Loads are unconditional: a tile past N reads a clamped
 // (valid) row and its product is discarded by the caller. A load under a lane
 // predicate becomes a branch whose join copies the value, i.e. an s_waitcnt
 // vmcnt(0) right after the load, which serialises the whole prefetch.
-template <int K, int T>
-struct WFrag {
-  h8 h[T][K / 32], l[T][K / 32];
-};
-template <int K, int N, int T>
-__device__ __forceinline__ void load_wf(WFrag<K, T>& w, const _Float16* __restrict__ hi, int wave, int lane) {
-  const int m = lane & 15, kq = lane >> 4;
-#pragma unroll
-  for (int tt = 0; tt < T; ++tt) {
-    const int n = min(16 * (wave + 4 * tt) + m, N - 1);
-#pragma unroll
-    for (int i = 0; i < K / 32; ++i) {
-      w.h[tt][i] = *reinterpret_cast<const h8*>(hi + n * K + 32 * i + 8 * kq);
-      w.l[tt][i] = *reinterpret_cast<const h8*>(hi + N * K + n * K + 32 * i + 8 * kq);
-    }
-  }
-}
-
-// 2^p and 2^-p with max |a| 2^p in [2^14, 2^15) (p clamped to +-100: a zero tile
-// gets 2^100; inf / NaN propagate through the products)
-__device__ __forceinline__ void pow2_scale(float amax, float& s, float& inv) {
-  const int e = (__builtin_bit_cast(int, amax) >> 23) & 255;
-  const int p = max(-100, min(100, 141 - e));
-  s = __builtin_bit_cast(float, (127 + p) << 23);
-  inv = __builtin_bit_cast(float, (127 - p) << 23);
-}
-
-// split-f16 A fragments of a [16][kLd] f32 LDS tile; inv undoes the A scale and
-// the 16 on W
-template <int K>
-struct AFrag {
-  h8 h[K / 32], l[K / 32];
-  float inv;
-};
-template <int K, int LD = kLd>
-__device__ __forceinline__ AFrag<K> load_a(const float* A, int lane) {
-  const int m = lane & 15, kq = lane >> 4;
-  f4 v[K / 32][2];
-  float mx = 0.f;
-#pragma unroll
-  for (int i = 0; i < K / 32; ++i) {
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      v[i][h] = *reinterpret_cast<const f4*>(A + m * LD + 32 * i + 8 * kq + 4 * h);
-#pragma unroll
-      for (int s = 0; s < 4; ++s) mx = fmaxf(mx, fabsf(v[i][h][s]));
-    }
-  }
-  float sc, inv;
-  pow2_scale(wmax(mx), sc, inv);
-  AFrag<K> f;
-  f.inv = inv * (1.f / 16.f);
-#pragma unroll
-  for (int i = 0; i < K / 32; ++i) split8(v[i][0] * sc, v[i][1] * sc, f.h[i], f.l[i]);
-  return f;
-}
-
-// two tiles (w, w + 4), two interleaved accumulation chains
-template <int K>
-__device__ __forceinline__ void gemm2(const WFrag<K, 2>& w, const AFrag<K>& a, f4& c0, f4& c1) {
-  c0 = f4{0.f, 0.f, 0.f, 0.f};
-  c1 = c0;
-#pragma unroll
-  for (int i = 0; i < K / 32; ++i) {
-    c0 = mma3(a.h[i], a.l[i], w.h[0][i], w.l[0][i], c0);
-    c1 = mma3(a.h[i], a.l[i], w.h[1][i], w.l[1][i], c1);
-  }
-  c0 *= a.inv;
-  c1 *= a.inv;
-}
-// one tile (w), two chains over the even / odd k blocks
-template <int K>
-__device__ __forceinline__ f4 gemm1(const WFrag<K, 1>& w, const AFrag<K>& a) {
-  f4 c[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-  for (int i = 0; i < K / 32; ++i) c[i & 1] = mma3(a.h[i], a.l[i], w.h[0][i], w.l[0][i], c[i & 1]);
-  return (c[0] + c[1]) * a.inv;
-}
-
-// The step's weight cache: the matrices k2 multiplies by (W_o_k, k < NG - 1:
-// [96][64]; W_hg_k, k >= 1: [128][96]) as f16 hi / lo planes of 16 W, each
-// twice: as stored ([N][K], the forward's NT operand) and transposed (the
-// backward's NN operand dx = dy W, again with k contiguous). Segment s at
-// halves dst: hi [R][C], lo [R][C], hi^T [C][R], lo^T [C][R]. Written from the
-// parameters by k0_wsplit (a step whose predecessor did not run k4 on this
-// workspace) and by k4 with every update, so k2 reads its fragments with no
-// conversion (the split of the f32 weights used to cost each of the ~70
-// workgroups ~700 VALU cycles per matrix stage).
-constexpr int kMaxSeg = 2 * kMaxG;
-struct WSeg {
-  int64_t src;  // float offset of the matrix in the parameters
-  int rows, cols;
-  int64_t dst;  // halves from the cache base
-  int64_t q0;   // first float4 of the segment in the k0 grid
-};
-struct WSplit {
-  int n;
-  WSeg s[kMaxSeg];
-};
 __device__ __forceinline__ void wsplit_store4(const WSplit& w, _Float16* __restrict__ base, int64_t i4, f4 p) {
 #pragma unroll
   for (int sg = 0; sg < kMaxSeg; ++sg) {
@@ -968,7 +751,7 @@ struct K2Args {
 // NG (= n_layers + 2 gated MLPs) is a template argument: every stage below is
 // straight-line code, so the register prefetches and their waits are exact.
 template <bool kTrain, int NG>
-__global__ void __launch_bounds__(256) k2_rows_kernel(K2Args a) {
+__global__ void __launch_bounds__(64 * kK2Waves) k2_rows_kernel(K2Args a) {
   // hgS, or the k1a slab of a prefetch workgroup (<= 80 KB in all: two
   // workgroups per CU, so the 2 n_rt-workgroup launch fits n_rt CUs)
   constexpr int kHgF = NG * kR * kLd > kR * kSlabLd ? NG * kR * kLd : kR * kSlabLd;
@@ -1132,7 +915,7 @@ __global__ void __launch_bounds__(256) k2_rows_kernel(K2Args a) {
   auto pub_max = [&](int mat, float mx) {
     if (a.maxS) {
       mx = wmax(mx);
-      if (lane == 0) *BCK(&a.maxS[(static_cast<int64_t>(mat) * a.n_rt + blockIdx.x) * 4 + wave], 4) = mx;
+      if (lane == 0) *BCK(&a.maxS[(static_cast<int64_t>(mat) * a.n_rt + blockIdx.x) * kK2Waves + wave], 4) = mx;
     }
   };
   if (kTrain) {  // U_0 from bU: thread -> column tid & 63, rows 4 (tid >> 6) ..
@@ -1307,7 +1090,7 @@ __global__ void __launch_bounds__(256) k2_rows_kernel(K2Args a) {
     if (a.maxS && lane == 0) {
 #pragma unroll
       for (int mat = 0; mat < 2 * NG; ++mat)
-        *BCK(&a.maxS[(static_cast<int64_t>(mat) * a.n_rt + blockIdx.x) * 4 + wave], 4) = 0.f;
+        *BCK(&a.maxS[(static_cast<int64_t>(mat) * a.n_rt + blockIdx.x) * kK2Waves + wave], 4) = 0.f;
     }
     return;
   }
@@ -1460,23 +1243,8 @@ __global__ void __launch_bounds__(256) k2_rows_kernel(K2Args a) {
 // halves; the split's Y^T tile (32 x 288) is loaded once per workgroup, split
 // into f16 hi / lo planes in LDS and shared by the four waves. Split-K partials
 // are added with float atomics into the bucket (zeroed by the previous k4).
-constexpr int kTM = 128, kTN = 32, kMaxJobs = 2 * kMaxG;
-// batch rows per split: measured 4 / 5 / 6 / 9 steps (124 / 152 / 180 / 248 VGPRs) at 60.2 / 60.3 /
-// 61.6 / 58.9 us per step on 256 CUs and 88.7 / 88.9 / 94.8 / 92.1 on a 64-CU stream
-#ifndef HBK_K3_STEPS
-#define HBK_K3_STEPS 9
-#endif
-constexpr int kK3Steps = HBK_K3_STEPS, kK3Rows = 32 * kK3Steps;  // batch rows per split (B = 1100: 4 splits)
-constexpr int kYLdH = kK3Rows + 8;                    // LDS row stride (halves) of the Y planes
-constexpr int kK3StepsNarrow = 4, kK3NarrowCUs = 96;
-// narrow streams: one workgroup may walk this many consecutive 128-row splits
-// (one partial slab per group). Measured at 3 on a 64-CU stream: k3 23.8 ->
-// 38.9 us (256 VGPRs, two workgroups per CU, the splits' latencies in series)
-// and k4 unchanged at 11.7 us with 3 slabs instead of 9, so it stays 1.
-#ifndef HBK_K3_GROUP
-#define HBK_K3_GROUP 1
-#endif
-constexpr int kK3GroupNarrow = HBK_K3_GROUP;
+// (The tile, kTM x kTN, and the steps per split, kK3Steps / kK3StepsNarrow with their
+// measurements, are the planner's: hbk_mlp_plan.h.)
 struct WJob {
   const float* X;  // [M][Bp]
   const float* Y;  // [N][Bp]
@@ -1748,8 +1516,7 @@ __global__ void __launch_bounds__(256) k3_wgrad_kernel(K3Args a) {
 // Granularity is the 16-row tile (the loads stay contiguous 16-B runs along the batch), not the
 // row: a live tile's dropped rows are still multiplied as zeros. HBK_STEP_DENSE=1 walks every
 // tile (A/B runs), as does a batch of more than kK3sMaxTiles tiles.
-constexpr int kK3sMaxR = 512;  // rows per split
-constexpr int kK3sMaxTiles = 512;  // row tiles of a batch whose live tiles are listed (one thread each)
+// (kK3sMaxR rows per split, kK3sMaxTiles listed row tiles: hbk_mlp_plan.h)
 // 8 waves of one 16-row M tile each: two waves per SIMD hide each other's latency (4 waves
 // of two M tiles ran one wave per SIMD at 256 VGPRs + AGPRs, 4.2 k cycles per 32-row step
 // against 1.9 k of issue). (4 M groups of two tiles x 2 column halves -- each B fragment read
@@ -1768,7 +1535,7 @@ struct K3sArgs {
   int start[kMaxJobs + 1];
   int n_jobs, S, n_rt, B;  // S: the slabs (the largest job split; a job with fewer zeroes the rest)
   int64_t Bp;
-  const float* maxS;  // [2 NG][n_rt][4]
+  const float* maxS;  // [2 NG][n_rt][kK2Waves]
   const float* pool32;
   const _Float16* pool16;
   const uint4* rinfo;
@@ -1791,8 +1558,7 @@ __device__ __forceinline__ int k3s_swz(int row, int ch) { return ch ^ (((row & 3
 // amortised over twice the MFMAs; 22.1 against 24.5 us), the generic jobs' 128. k3s is bound
 // per CU (two workgroups on one CU each ran 2.2x slower), not by a chip-wide resource, and
 // neither fewer VALU, half the LDS fragment traffic nor contiguous row loads moved it
-// (profiles/r06_ab_step.log)
-constexpr int kK3sNbtRaw = 16, kK3sNbtGen = 8;
+// (profiles/r06_ab_step.log): kK3sNbtRaw = 16, kK3sNbtGen = 8 (hbk_mlp_plan.h)
 static_assert(kD % (16 * kK3sNbtRaw) == 0, "the input layer's tiles are all live");
 struct K3sShared {
   static constexpr int kLdY = 48;  // generic: LDS column of 32 rows + 16 pad halves (conflict-free b128 reads)
@@ -1952,7 +1718,7 @@ __device__ __forceinline__ void k3s_body(const K3sArgs& a, const K3sJob& jb, int
   // 12-step workgroup's 24): the gradient's per-tile maxima, the gradient of steps 0 .. 2,
   // the input layer's row information and mask words (for LDS), and the activation of steps 0
   // and 1 (the input layer's through row information loaded into registers here as well)
-  static_assert(kK3sMaxR / 16 * 4 <= 128, "maxS: two entries per lane");
+  static_assert(kK2Waves == 4 && kK3sMaxR / 16 * kK2Waves <= 128, "maxS: a tile's entries are q >> 2, q & 3; two entries per lane");
   float mxv[2];
   {
     const int n4 = 4 * (cend - ct0);
@@ -1960,7 +1726,7 @@ __device__ __forceinline__ void k3s_body(const K3sArgs& a, const K3sJob& jb, int
     for (int i = 0; i < 2; ++i) {
       const int q = lane + 64 * i;
       const int t = tile_row(ct0 + (q >> 2)) >> 4;
-      const float v = *BCK(&a.maxS[(static_cast<int64_t>(jb.mat) * a.n_rt + t) * 4 + (q & 3)], 4);
+      const float v = *BCK(&a.maxS[(static_cast<int64_t>(jb.mat) * a.n_rt + t) * kK2Waves + (q & 3)], 4);
       mxv[i] = q < n4 ? v : 0.f;
     }
   }
@@ -2208,7 +1974,8 @@ __global__ void __launch_bounds__(kK3sThr, kOcc) k3s_kernel(K3sArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     bool lv = false;
     if (tid < a.n_rt) {
-      const f4 v = *BCK(reinterpret_cast<const f4*>(a.maxS + (static_cast<int64_t>(a.n_jobs - 1) * a.n_rt + tid) * 4), 16);
+      static_assert(kK2Waves == 4, "a tile's maxima are one float4");
+      const f4 v = *BCK(reinterpret_cast<const f4*>(a.maxS + (static_cast<int64_t>(a.n_jobs - 1) * a.n_rt + tid) * kK2Waves), 16);
       lv = v[0] != 0.f || v[1] != 0.f || v[2] != 0.f || v[3] != 0.f;
     }
     const unsigned long long bal = __ballot(lv);
@@ -2538,622 +2305,6 @@ __global__ void __launch_bounds__(256) k4_update_kernel(K4Args a) {
   }
 }
 
-
-// ---------------------------------------------------------- evaluation ----
-// The validation / testing passes of train_epoch (trainer.py:496-566): a
-// forward with input dropout over hundreds of thousands of rows (the default
-// validation pass is 500 batches of 50 + 1,000 rows, the testing pass 500 of
-// 50 + 50), reduced to prediction counts. The input layer is a real GEMM here
-// ([rows, 1536] x [1536, 128]), so it gets a throughput kernel of its own,
-// kv_gemm: the LayerNorm is folded into the GEMM's epilogue,
-//   (LN(x) g + b) W^T = rs (x W'^T - mu c1) + c0,  W' = W o g (columns scaled),
-//   c1[n] = sum_k W'[n][k],  c0[n] = sum_k b[k] W[n][k],
-// so the product runs on the raw (dropped-out) rows: an f16 pool row is exact
-// in f16 (its hi part; no lo), two products per 32-deep block instead of
-// three. mu / rs come from the same loaded values (per-lane float sums of 8,
-// accumulated in double). W' (f16 hi / lo planes of 16 W') is staged through
-// LDS in 64-deep chunks, double-buffered, shared by 8 waves of 32 rows each;
-// the rows stream from HBM straight into MFMA A fragments, prefetched two
-// chunks ahead. The pre-bias HG0 rows go to a slab that k2_rows_kernel
-// <false> (the inference chain, with its counters) reads as its one K-split.
-constexpr int kKvKC = 64, kKvChunks = kD / kKvKC;
-constexpr int kKvMaxSeg = kEvalMaxSeg;
-struct KvArgs {
-  const void* pool;      // f32 or f16 rows of 1536
-  int64_t n_pool;
-  const int32_t* idx;    // row r -> pool row idx[r]; NULL: r0 + r modulo n_pool
-  int64_t rows, r0;      // this launch's rows; r0 = their first index in the pass (dropout counter)
-  const _Float16* wq;    // [2][128][1536] hi / lo planes of 16 W'
-  const float* c0;
-  const float* c1;
-  float drop_p;
-  uint64_t seed;
-  // the rest of the network (parameter offsets; weight cache planes as k2 reads them)
-  const float* P;
-  int64_t b_hg[kMaxG], b_o[kMaxG], w_o[kMaxG], ln_g[kMaxG], ln_b[kMaxG];
-  const _Float16* wc;
-  int64_t c_o[kMaxG], c_hg[kMaxG];
-  float act_thr;
-  float* counts;  // [4]: counts[2 label] += #(p >= act_thr), counts[2 label + 1] += #(p > act_thr)
-  int label;
-  float* prob;    // [rows] or NULL
-  // several pools in one launch (hbk_mlp_eval_count_multi; nseg = 0: the fields above): workgroup
-  // b of segment s = the first segment with b < seg_tile0[s + 1] takes pool s's tile b - seg_tile0[s]
-  int nseg;
-  int seg_tile0[kKvMaxSeg + 1];
-  const void* seg_pool[kKvMaxSeg];
-  int64_t seg_npool[kKvMaxSeg], seg_rows[kKvMaxSeg], seg_r0[kKvMaxSeg];
-  uint64_t seg_seed[kKvMaxSeg];
-  float* seg_counts[kKvMaxSeg];
-  int seg_label[kKvMaxSeg];
-  int lap_tiles;  // the lap form (kLap > 0): workgroups per lap set, ceil(n_pool / 128); rows = whole sets
-};
-
-__global__ void __launch_bounds__(256) kv_prep_kernel(const float* __restrict__ P, int64_t w0, int64_t g_in,
-                                                      int64_t b_in, _Float16* __restrict__ wq, float* c0,
-                                                      float* c1) {
-  __shared__ double red[2][4];
-  const int n = blockIdx.x, tid = threadIdx.x;
-  const float* W = P + w0 + int64_t(n) * kD;
-  double s0 = 0.0, s1 = 0.0;
-  for (int k = 2 * tid; k < kD; k += 512) {
-    const float wa = W[k], wb = W[k + 1];
-    const float ga = wa * P[g_in + k], gb = wb * P[g_in + k + 1];
-    uint32_t hi, lo;
-    split_pair(16.f * ga, 16.f * gb, hi, lo);
-    *reinterpret_cast<uint32_t*>(wq + int64_t(n) * kD + k) = hi;
-    *reinterpret_cast<uint32_t*>(wq + int64_t(kH2) * kD + int64_t(n) * kD + k) = lo;
-    s1 += double(ga) + double(gb);
-    s0 += double(P[b_in + k]) * wa + double(P[b_in + k + 1]) * wb;
-  }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    s0 += __shfl_xor(s0, o, 64);
-    s1 += __shfl_xor(s1, o, 64);
-  }
-  if ((tid & 63) == 0) {
-    red[0][tid >> 6] = s0;
-    red[1][tid >> 6] = s1;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    c0[n] = static_cast<float>((red[0][0] + red[0][1]) + (red[0][2] + red[0][3]));
-    c1[n] = static_cast<float>((red[1][0] + red[1][1]) + (red[1][2] + red[1][3]));
-  }
-}
-
-#ifndef HBK_KV_ABLATE
-#define HBK_KV_ABLATE 0  // profiling builds: 1 skips the network phase, 2 the dropout mask
-#endif
-// The streamed rows are read once: non-temporal loads (HBK_KV_NT, default on)
-// keep them from evicting W', which every tile re-reads, from the XCD's L2.
-#ifndef HBK_KV_NT
-#define HBK_KV_NT 1
-#endif
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint4 load_rows4(const uint4* p) {
-#if HBK_KV_NT
-  const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
-  return uint4{v[0], v[1], v[2], v[3]};
-#else
-  return *p;
-#endif
-}
-
-// kF16: the rows are f16 (exact in hi); else f32 (split hi / lo).
-// W' chunks reach LDS by global->LDS DMA (global_load_lds_dwordx4: no register
-// staging, so no spills at 8 waves x ~240 VGPRs), issued two chunks ahead. The
-// DMA writes a wave's 64 x 16 B contiguously, so the image is unpadded
-// [plane][n][64 halves] rows with the 16-B pieces XOR-swizzled by (n >> 1) & 7
-// on the SOURCE address (the B-fragment reads of 16 lanes then hit 16
-// distinct 4-bank groups). The chunk's barrier waits with a counted vmcnt
-// (the DMA retired, the next rows' loads still in flight) and a raw s_barrier:
-// __syncthreads() would emit vmcnt(0) and drain the row prefetch.
-constexpr int kKvPiece = 8;  // 16-B pieces per 64-deep row of a chunk
-__device__ __forceinline__ int kv_swz(int n) { return (n >> 1) & 7; }
-constexpr int kNetWLd = 104, kAld = 100;  // LDS row strides: weight halves (K <= 96), activation floats
-// W: waves per workgroup, 8 (f16 rows: two 16-row tiles per wave) or 16 (one tile per wave:
-// twice the waves per CU to hide the stream's latency, at most 128 VGPRs each)
-// kLap = 2, the lap form (f16 pools read in order, 8 waves): a pass that reads its pool several times
-// over evaluates every pool row once per lap, and only the dropout mask (a hash of the row's index in the
-// pass) differs between the laps. So a wave's two tiles are two laps of the SAME 16 pool rows: one load
-// of the raw rows per chunk, masked and converted once per lap: 1.5 + 3 KB per row evaluation against
-// 3 + 3 KB. The launch covers whole lap sets: set q is the row evaluations [2 q n_pool, 2 (q + 1) n_pool)
-// of the launch, its workgroup t the pool rows (r0 + 16 W t ..) % n_pool (a wrap inside a tile is per
-// lane; the last tile's rows past n_pool are dead). Every row evaluation keeps its values, chunk order
-// and MFMA sequence, so prob and the counts are those of the plain form, bit for bit. (Four laps per wave
-// need 128 accumulator registers of the 256: hipcc spills inside the chunk loop)
-template <bool kF16, int NG, int W, int kLap = 0>
-__global__ void __launch_bounds__(64 * W) kv_gemm_kernel(KvArgs a0) {
-  static_assert(kLap == 0 || (kF16 && W == 8 && kLap == 2), "the lap form: f16 rows, 8 waves of two laps");
-  // this workgroup's pool (segment): its fields replace the single-pool ones (uniform)
-  KvArgs a = a0;
-  int blk = static_cast<int>(blockIdx.x);
-  if (a0.nseg > 0) {
-    int sg = 0;
-#pragma unroll
-    for (int q = 1; q < kKvMaxSeg; ++q) sg += (q < a0.nseg && blk >= a0.seg_tile0[q]) ? 1 : 0;
-    blk -= a0.seg_tile0[sg];
-    a.pool = a0.seg_pool[sg];
-    a.n_pool = a0.seg_npool[sg];
-    a.idx = nullptr;
-    a.rows = a0.seg_rows[sg];
-    a.r0 = a0.seg_r0[sg];
-    a.seed = a0.seg_seed[sg];
-    a.counts = a0.seg_counts[sg];
-    a.label = a0.seg_label[sg];
-    a.prob = nullptr;
-  }
-  // ONE __shared__ object: beside a second one hipcc drains the DMA (vmcnt(0))
-  // before every chunk's first LDS read. GEMM phase: the W' ring (the row
-  // statistics reuse buffer 0 after it); network phase: a stage's weight planes
-  // at 0, the waves' activation tiles after them, two counters last.
-  constexpr int kWBuf = 3;  // W' ring: chunk c + 2's DMA is issued during chunk c (kWBuf - 1 == 2 assumed below)
-  constexpr int kRT = kLap ? kLap : (kF16 && W == 8) ? 2 : 1;  // 16-row tiles per wave (f32 rows: one, for the split's registers)
-  constexpr int kAT = kLap ? 1 : kRT;         // of them loaded: the laps share one tile of raw rows
-  constexpr int kThr = 64 * W;
-  constexpr int kGemmBytes = kWBuf * 2 * kH2 * kKvKC * 2;
-  constexpr int kWsBytes = 2 * kH2 * kNetWLd * 2;
-  constexpr int kActBytes = W * 16 * kRT * kAld * 4;
-  constexpr int kLdsBytes = (kGemmBytes > kWsBytes + kActBytes ? kGemmBytes : kWsBytes + kActBytes) + 16;
-  static_assert(kLdsBytes <= 160 * 1024, "one workgroup's LDS");
-  __shared__ __attribute__((aligned(16))) unsigned char smem[kLdsBytes];
-  auto wb = reinterpret_cast<_Float16 (*)[2][kH2][kKvKC]>(smem);  // [buf][hi / lo][n][k] (swizzled pieces)
-  float (*stS)[16 * kRT][2] = reinterpret_cast<float (*)[16 * kRT][2]>(smem);
-  static_assert(sizeof(float) * W * 16 * kRT * 2 <= kWsBytes, "statistics: below the activation tiles");
-#ifndef HBK_KV_DEPTH
-#define HBK_KV_DEPTH 2
-#endif
-  constexpr int kDepth = kF16 ? HBK_KV_DEPTH : 2;  // A chunks in flight (this one + kDepth - 1 ahead)
-  constexpr int kBGroup = kDepth > 2 ? 2 : 4;       // column tiles whose B fragments may be in flight together
-  constexpr int kU = kF16 ? 1 : 2;  // 16-B loads per 8 elements
-  constexpr int kALoads = kAT * 2 * kU;  // per chunk
-  constexpr int kTile = W * 16 * kRT;
-  constexpr int kDma = 32 / W;  // W' DMA instructions per wave and chunk (2 planes x 128 rows of 128 B)
-  static_assert(kALoads * (kDepth - 1) + kDma < 16, "the counted waits use vmcnt's low field");
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, m = lane & 15, kq = lane >> 4;
-  const int64_t tile0 = int64_t(blk) * kTile;
-  // the lap form: the set's first row evaluation, and the wave's first row of the set's lap 0
-  const int64_t lap_s = kLap ? int64_t(blk / max(a.lap_tiles, 1)) * kLap * a.n_pool : 0;
-  const int64_t lap_b = kLap ? int64_t(blk % max(a.lap_tiles, 1)) * (16 * W) + 16 * wave : 0;
-  // row j of the wave's tile rt: its row evaluation in the launch, and whether there is one
-  auto row_of = [&](int rt, int j, bool& live) -> int64_t {
-    if constexpr (kLap > 0) {
-      const int64_t r = lap_s + rt * a.n_pool + lap_b + j;
-      live = lap_b + j < a.n_pool && r < a.rows;
-      return r;
-    } else {
-      const int64_t r = tile0 + 16 * kRT * wave + 16 * rt + j;
-      live = r < a.rows;
-      return r;
-    }
-  };
-  const char* rp[kAT];
-  uint32_t rid[kRT];
-  if constexpr (kLap > 0) {
-    const int64_t b = min(lap_b + m, a.n_pool - 1);  // (dead rows repeat the pool's last one)
-    const int64_t pr = min(max((a.r0 + b) % a.n_pool, int64_t(0)), a.n_pool - 1);  // lap_s is whole laps
-    rp[0] = static_cast<const char*>(a.pool) + pr * kD * 2;
-#pragma unroll
-    for (int rt = 0; rt < kRT; ++rt) rid[rt] = static_cast<uint32_t>(a.r0 + lap_s + rt * a.n_pool + b);
-  } else {
-#pragma unroll
-  for (int rt = 0; rt < kRT; ++rt) {
-    const int64_t r = min(tile0 + 16 * kRT * wave + 16 * rt + m, a.rows - 1);
-    int64_t pr = a.idx ? static_cast<int64_t>(a.idx[r]) : (a.r0 + r) % a.n_pool;
-    pr = min(max(pr, int64_t(0)), a.n_pool - 1);
-    rp[rt] = static_cast<const char*>(a.pool) + pr * kD * (kF16 ? 2 : 4);
-    rid[rt] = static_cast<uint32_t>(a.r0 + r);
-  }
-  }
-  const uint64_t seed = a.seed;
-  const uint32_t s0 = static_cast<uint32_t>(seed), s1 = static_cast<uint32_t>(seed >> 32) * 0x27D4EB2Fu;
-  const uint32_t thr = static_cast<uint32_t>(a.drop_p * 65536.f + 0.5f);
-  const float keep = a.drop_p > 0.f ? 1.f / (1.f - a.drop_p) : 1.f;
-  uint4 ar[kDepth][kAT][2][kU];
-  auto load_rows = [&](int c, int slot) {
-#pragma unroll
-    for (int rt = 0; rt < kAT; ++rt)
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb) {
-        const int k = kKvKC * c + 32 * kb + 8 * kq;
-#pragma unroll
-        for (int u = 0; u < kU; ++u)
-          ar[slot][rt][kb][u] = load_rows4(reinterpret_cast<const uint4*>(rp[rt] + int64_t(k) * (kF16 ? 2 : 4) + 16 * u));
-      }
-  };
-  // W' chunk c -> buffer buf: 2 planes x 128 rows x 8 pieces = 2,048 pieces, 4 DMA
-  // instructions per wave (8 rows each); lane l of instruction j writes piece
-  // (row 8 (4 wave + j) + l / 8, slot l % 8), reading the source piece slot ^ swz(row)
-  auto dma_w = [&](int c, int buf) {
-#pragma unroll
-    for (int j = 0; j < kDma; ++j) {
-      const int row8 = kDma * wave + j;              // 0 .. 31: plane row8 / 16, rows 8 (row8 % 16) ..
-      const int pl = row8 >> 4, n = 8 * (row8 & 15) + (lane >> 3), pc = (lane & 7) ^ kv_swz(n);
-      const _Float16* src = a.wq + int64_t(pl) * kH2 * kD + int64_t(n) * kD + kKvKC * c + kKvPiece * pc;
-      __builtin_amdgcn_global_load_lds(src, &wb[buf][pl][8 * (row8 & 15)][0], 16, 0, 0);
-    }
-  };
-  // prologue: chunks 0 and 1 (W' buffers 0, 1; A slots 0, 1); chunk 0 waited for here,
-  // chunk 1 at the end of chunk 0
-  dma_w(0, 0);
-  load_rows(0, 0);
-  dma_w(1, 1);
-#pragma unroll
-  for (int d = 1; d < kDepth; ++d) load_rows(d, d);
-  __builtin_amdgcn_s_waitcnt((kALoads * (kDepth - 1) + kDma) | (0x7 << 4) | (0xF << 8));  // chunk 0 in (the later chunks' DMA and rows may fly)
-  dma_barrier();
-  f4 acc[kRT][8];
-#pragma unroll
-  for (int rt = 0; rt < kRT; ++rt)
-#pragma unroll
-    for (int ct = 0; ct < 8; ++ct) acc[rt][ct] = f4{0.f, 0.f, 0.f, 0.f};
-  double sd1[kRT], sd2[kRT];
-#pragma unroll
-  for (int rt = 0; rt < kRT; ++rt) sd1[rt] = sd2[rt] = 0.0;
-  static_assert(kKvChunks % kDepth == 0, "the A ring's slots must be compile-time");
-  int buf = 0;  // W' buffer of chunk c (c % kWBuf; a run-time LDS offset, the A slot is unrolled)
-#pragma unroll 1
-  for (int cb = 0; cb < kKvChunks; cb += kDepth)
-#pragma unroll
-  for (int slot = 0; slot < kDepth; ++slot) {
-    const int c = cb + slot;
-    const int bnext = buf == 0 ? kWBuf - 1 : buf - 1;  // (c + 2) % kWBuf
-    // this chunk's A values (dropout mask, row sums, split) first: their loads are
-    // ordinary global loads, so no DMA may be outstanding when they are used
-    h8 ah[kRT][2], al[kRT][2];
-    float t1[kRT], t2[kRT];
-#pragma unroll
-    for (int rt = 0; rt < kRT; ++rt) t1[rt] = t2[rt] = 0.f;
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-      for (int rt = 0; rt < kRT; ++rt) {
-        float v[8];
-        if (kF16) {
-          const h8 hv = __builtin_bit_cast(h8, ar[slot][kLap ? 0 : rt][kb][0]);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] = static_cast<float>(hv[e]);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] = __builtin_bit_cast(float, (&ar[slot][kLap ? 0 : rt][kb][e >> 2].x)[e & 3]);
-        }
-        if (!(HBK_KV_ABLATE & 2) && a.drop_p > 0.f) {  // nn.Dropout's mask (the 1 / (1 - p) scale is applied after the GEMM)
-          const uint32_t base = rid[rt] * (kD / 2) + ((kKvKC * c + 32 * kb + 8 * kq) >> 1);
-#pragma unroll
-          for (int e = 0; e < 8; e += 2) {
-            const uint32_t hsh = drop_hash(s0, s1, base + (e >> 1));
-            v[e] = (hsh & 0xFFFFu) < thr ? 0.f : v[e];
-            v[e + 1] = (hsh >> 16) < thr ? 0.f : v[e + 1];
-          }
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          t1[rt] += v[e];
-          t2[rt] += v[e] * v[e];
-        }
-        if (kF16) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) ah[rt][kb][e] = static_cast<_Float16>(v[e]);  // exact
-        } else {
-          split8(f4{v[0], v[1], v[2], v[3]}, f4{v[4], v[5], v[6], v[7]}, ah[rt][kb], al[rt][kb]);
-        }
-      }
-#pragma unroll
-    for (int rt = 0; rt < kRT; ++rt) {
-      sd1[rt] += double(t1[rt]);
-      sd2[rt] += double(t2[rt]);
-    }
-    // unconditional (past the end: a clamped re-read) so that the loop has no
-    // branches and hipcc's counted waits stay exact across the back edge
-    dma_w(min(c + 2, kKvChunks - 1), bnext);  // its readers (chunk c - 1) passed the last barrier
-    load_rows(min(c + kDepth, kKvChunks - 1), slot);
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-      for (int ct = 0; ct < 8; ++ct) {
-        const int n = 16 * ct + m, pc = (4 * kb + kq) ^ kv_swz(n);
-        const h8 bh = *reinterpret_cast<const h8*>(&wb[buf][0][n][kKvPiece * pc]);
-        const h8 bl = *reinterpret_cast<const h8*>(&wb[buf][1][n][kKvPiece * pc]);
-#pragma unroll
-        for (int rt = 0; rt < kRT; ++rt) {
-          acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[rt][kb], bh, acc[rt][ct], 0, 0, 0);
-          acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[rt][kb], bl, acc[rt][ct], 0, 0, 0);
-          if (!kF16) acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[rt][kb], bh, acc[rt][ct], 0, 0, 0);
-        }
-        if ((ct & (kBGroup - 1)) == kBGroup - 1) __builtin_amdgcn_sched_barrier(0);  // bound the B fragments in flight (registers)
-      }
-    // chunk c + 1's DMA and rows retired (chunk c + 2's, issued above, may still fly), then the barrier.
-    // The sched_barriers keep the next chunk's conversions below the counted wait: hoisted
-    // above it, hipcc guards them with vmcnt(0) (DMA and row loads pending together)
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_waitcnt((kALoads * (kDepth - 1) + kDma) | (0x7 << 4) | (0xF << 8));  // chunk c + 1 in
-    __builtin_amdgcn_s_waitcnt((0x3F & 0xF) | ((0x3F >> 4) << 14) | (0x7 << 4) | (0x0 << 8));  // lgkmcnt(0)
-    dma_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    buf = buf == kWBuf - 1 ? 0 : buf + 1;
-  }
-  __builtin_amdgcn_s_waitcnt((0x7 << 4) | (0xF << 8));  // vmcnt(0): the clamped re-reads (into buffers 0, 1) in
-  dma_barrier();
-  // row statistics: the 4 lanes m + 16 kq hold a row's parts
-  // (buffer 0's last readers, chunk kKvChunks - 2, passed that chunk's barrier)
-#pragma unroll
-  for (int rt = 0; rt < kRT; ++rt) {
-#pragma unroll
-    for (int o = 16; o < 64; o <<= 1) {
-      sd1[rt] += __shfl_xor(sd1[rt], o, 64);
-      sd2[rt] += __shfl_xor(sd2[rt], o, 64);
-    }
-    if (kq == 0) {
-      const double mu = sd1[rt] * (1.0 / kD);
-      const double var = fmax(sd2[rt] * (1.0 / kD) - mu * mu, 0.0);
-      const double kp = double(keep);
-      stS[wave][16 * rt + m][0] = static_cast<float>(kp * mu);                              // mean of the dropped-out row
-      stS[wave][16 * rt + m][1] = static_cast<float>(1.0 / sqrt(kp * kp * var + double(kLnEps)));  // its 1 / std
-    }
-  }
-  dma_barrier();
-#if HBK_KV_ABLATE & 1  // profiling build: the input GEMM only (no network, no counts)
-  if (a.rows > 0) return;
-#endif
-  // ---- the rest of the network, per wave on its kRT row tiles ----
-  // HG0 = rs (acc / 16 keep - mu c1) + c0 + b; U0 = silu(H) G into the wave's
-  // activation tile (the lane holds hidden column j = 16 ct + m and gate column
-  // 64 + j: ct and ct + 4)
-  float* A = reinterpret_cast<float*>(smem + kWsBytes) + wave * (16 * kRT * kAld);
-  {
-    const float ks = keep * (1.f / 16.f);
-    float mu[kRT][4], rs[kRT][4];
-#pragma unroll
-    for (int rt = 0; rt < kRT; ++rt)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        mu[rt][e] = stS[wave][16 * rt + 4 * kq + e][0];
-        rs[rt][e] = stS[wave][16 * rt + 4 * kq + e][1];
-      }
-    lds_barrier();  // every wave has its statistics: the activation tiles may overwrite them
-#pragma unroll
-    for (int ct = 0; ct < 4; ++ct) {
-      const int j = 16 * ct + m;
-      const float c0h = a.c0[j] + a.P[a.b_hg[0] + j], c0g = a.c0[kH + j] + a.P[a.b_hg[0] + kH + j];
-      const float c1h = a.c1[j], c1g = a.c1[kH + j];
-#pragma unroll
-      for (int rt = 0; rt < kRT; ++rt)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float h = rs[rt][e] * (acc[rt][ct][e] * ks - mu[rt][e] * c1h) + c0h;
-          const float g = rs[rt][e] * (acc[rt][ct + 4][e] * ks - mu[rt][e] * c1g) + c0g;
-          A[(16 * rt + 4 * kq + e) * kAld + j] = h * sigm_fast(h) * g;
-        }
-    }
-  }
-  // weight stages: W_o_0, W_hg_1, W_o_1, ..., W_hg_{NG-1}: (cache offset, N, K); each
-  // stage's f16 hi / lo planes staged into LDS once for the 8 waves, the next
-  // stage's loaded into registers while the current one runs
-  _Float16 (*wS)[kH2][kNetWLd] = reinterpret_cast<_Float16 (*)[kH2][kNetWLd]>(smem);
-  constexpr int kStages = 2 * (NG - 1);
-  auto st_off = [&](int st) { return (st & 1) ? a.c_hg[st / 2 + 1] : a.c_o[st / 2]; };
-  auto st_n = [](int st) { return (st & 1) ? kH2 : kL; };
-  auto st_k = [](int st) { return (st & 1) ? kL : kH; };
-  // (six named registers, not an array: an array here stays in scratch memory
-  // beside the GEMM phase's register pressure)
-  uint4 wr0, wr1, wr2, wr3, wr4, wr5;
-  constexpr int kWr = 3072 / kThr;  // staged 16-B pieces per thread (W_hg: 2 planes x 1,536)
-  auto piece = [&](int st, int j, int& pl, int& n, int& k) {
-    const int N = st_n(st), K = st_k(st), pieces = N * K / 8;  // per plane
-    const int q = min(tid + kThr * j, 2 * pieces - 1), e0 = q % pieces;
-    pl = q / pieces;
-    n = (8 * e0) / K;
-    k = 8 * e0 - n * K;
-  };
-  auto load1 = [&](int st, int j, uint4& v) {
-    int pl, n, k;
-    piece(st, j, pl, n, k);
-    v = *reinterpret_cast<const uint4*>(a.wc + st_off(st) + int64_t(pl) * st_n(st) * st_k(st) + n * st_k(st) + k);
-  };
-  auto store1 = [&](int st, int j, const uint4& v) {  // (threads past the pieces repeat the last one)
-    int pl, n, k;
-    piece(st, j, pl, n, k);
-    *reinterpret_cast<uint4*>(&wS[pl][n][k]) = v;
-  };
-  auto load_w = [&](int st) {
-    load1(st, 0, wr0);
-    load1(st, 1, wr1);
-    load1(st, 2, wr2);
-    if constexpr (kWr > 3) {
-      load1(st, 3, wr3);
-      load1(st, 4, wr4);
-      load1(st, 5, wr5);
-    }
-  };
-  auto store_w = [&](int st) {
-    store1(st, 0, wr0);
-    store1(st, 1, wr1);
-    store1(st, 2, wr2);
-    if constexpr (kWr > 3) {
-      store1(st, 3, wr3);
-      store1(st, 4, wr4);
-      store1(st, 5, wr5);
-    }
-  };
-  load_w(0);
-  store_w(0);
-  lds_barrier();
-  const float* P = a.P;
-#pragma unroll
-  for (int st = 0; st < kStages; ++st) {
-    if (st + 1 < kStages) load_w(st + 1);  // the next stage's planes, in flight during this one
-    if ((st & 1) == 0) {
-      // S = U W_o^T + b_o (K 64, N 96: 6 column tiles), then LayerNorm k -> X (A, K 96)
-      const int k = st / 2;
-      AFrag<kH> af[kRT];
-#pragma unroll
-      for (int rt = 0; rt < kRT; ++rt) af[rt] = load_a<kH, kAld>(A + 16 * rt * kAld, lane);
-      f4 c[kRT][6];
-#pragma unroll
-      for (int ct = 0; ct < 6; ++ct) {
-#pragma unroll
-        for (int rt = 0; rt < kRT; ++rt) c[rt][ct] = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int i = 0; i < kH / 32; ++i) {
-          const h8 bh = *reinterpret_cast<const h8*>(&wS[0][16 * ct + m][32 * i + 8 * kq]);
-          const h8 bl = *reinterpret_cast<const h8*>(&wS[1][16 * ct + m][32 * i + 8 * kq]);
-#pragma unroll
-          for (int rt = 0; rt < kRT; ++rt) c[rt][ct] = mma3(af[rt].h[i], af[rt].l[i], bh, bl, c[rt][ct]);
-        }
-      }
-      float bo[6], gm[6], bt[6];
-#pragma unroll
-      for (int ct = 0; ct < 6; ++ct) {
-        bo[ct] = P[a.b_o[k] + 16 * ct + m];
-        gm[ct] = P[a.ln_g[k] + 16 * ct + m];
-        bt[ct] = P[a.ln_b[k] + 16 * ct + m];
-      }
-#pragma unroll
-      for (int rt = 0; rt < kRT; ++rt) {
-        float sm[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ct = 0; ct < 6; ++ct)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            c[rt][ct][e] = c[rt][ct][e] * af[rt].inv + bo[ct];
-            sm[e] += c[rt][ct][e];
-          }
-        float mu[4], sq[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) mu[e] = rsum16(sm[e]) * (1.f / kL);
-#pragma unroll
-        for (int ct = 0; ct < 6; ++ct)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) sq[e] += (c[rt][ct][e] - mu[e]) * (c[rt][ct][e] - mu[e]);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) sq[e] = __builtin_amdgcn_rsqf(rsum16(sq[e]) * (1.f / kL) + kLnEps);
-#pragma unroll
-        for (int ct = 0; ct < 6; ++ct)
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            A[(16 * rt + 4 * kq + e) * kAld + 16 * ct + m] = (c[rt][ct][e] - mu[e]) * sq[e] * gm[ct] + bt[ct];
-      }
-    } else {
-      // HG = X W_hg^T + b (K 96, N 128), gate in the epilogue -> U (A, K 64)
-      const int k = st / 2 + 1;
-      AFrag<kL> af[kRT];
-#pragma unroll
-      for (int rt = 0; rt < kRT; ++rt) af[rt] = load_a<kL, kAld>(A + 16 * rt * kAld, lane);
-      f4 c[kRT][8];
-#pragma unroll
-      for (int ct = 0; ct < 8; ++ct) {
-#pragma unroll
-        for (int rt = 0; rt < kRT; ++rt) c[rt][ct] = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int i = 0; i < kL / 32; ++i) {
-          const h8 bh = *reinterpret_cast<const h8*>(&wS[0][16 * ct + m][32 * i + 8 * kq]);
-          const h8 bl = *reinterpret_cast<const h8*>(&wS[1][16 * ct + m][32 * i + 8 * kq]);
-#pragma unroll
-          for (int rt = 0; rt < kRT; ++rt) c[rt][ct] = mma3(af[rt].h[i], af[rt].l[i], bh, bl, c[rt][ct]);
-        }
-      }
-#pragma unroll
-      for (int ct = 0; ct < 4; ++ct) {
-        const int col = 16 * ct + m;
-        const float bh = P[a.b_hg[k] + col], bg = P[a.b_hg[k] + kH + col];
-#pragma unroll
-        for (int rt = 0; rt < kRT; ++rt)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float h = c[rt][ct][e] * af[rt].inv + bh, g = c[rt][ct + 4][e] * af[rt].inv + bg;
-            A[(16 * rt + 4 * kq + e) * kAld + col] = h * sigm_fast(h) * g;
-          }
-      }
-    }
-    if (st + 1 < kStages) {
-      lds_barrier();  // every wave is done with this stage's planes
-      store_w(st + 1);
-      lds_barrier();
-    }
-  }
-  // z = U w_out + b_out: lane -> row lane / 4 of a tile, 16 columns; sigmoid, counts
-  float* cntS = reinterpret_cast<float*>(smem + kWsBytes + kActBytes);
-  if (tid < 2) cntS[tid] = 0.f;
-  lds_barrier();
-  {
-    const int r = lane >> 2, c0 = 16 * (lane & 3);
-    float wo[16];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) wo[q] = P[a.w_o[NG - 1] + c0 + q];
-    const float bz = P[a.b_o[NG - 1]];
-    int ge = 0, gt = 0;
-#pragma unroll
-    for (int rt = 0; rt < kRT; ++rt) {
-      float z = 0.f;
-#pragma unroll
-      for (int q = 0; q < 16; ++q) z = fmaf(A[(16 * rt + r) * kAld + c0 + q], wo[q], z);
-      z += dpp_f<0xB1>(z);  // quad_perm: lanes ^ 1, ^ 2 hold the row's other columns
-      z += dpp_f<0x4E>(z);
-      z += bz;
-      bool live;
-      const int64_t row = row_of(rt, r, live);
-      live = live && (lane & 3) == 0;
-      const float p = sigm_fast(z);
-      if (live && a.prob) a.prob[row] = p;
-      ge += __popcll(__ballot(live && p >= a.act_thr));
-      gt += __popcll(__ballot(live && p > a.act_thr));
-    }
-    if (lane == 0) {
-      if (ge) atomicAdd(&cntS[0], static_cast<float>(ge));
-      if (gt) atomicAdd(&cntS[1], static_cast<float>(gt));
-    }
-  }
-  lds_barrier();
-  if (tid < 2 && cntS[tid] != 0.f) atomicAdd(a.counts + 2 * a.label + tid, cntS[tid]);
-}
-
-
-// After the passes (trainer.py:509-536, :549-566): the validation false
-// positives per hour (count / hours in float32, as torch divides an integer
-// count tensor by a Python float), recall, the testing rates, and the dynamic
-// negative weight (x ratio above the target rate, / ratio with a floor of 1
-// otherwise) written into the schedule rows of every later step.
-struct EvalFinish {
-  const float* cv;  // validation counts [4] (label 0: >=, >; label 1: >=, >)
-  const float* ct;  // testing counts [4] or NULL
-  float n_neg_v, n_pos_v, n_neg_t, n_pos_t;
-  float hours_v;    // n_neg_v * 1.44 / 3600, rounded to float32 on the host
-  float target, ratio;  // ratio <= 0: no dynamic adjustment
-  float* sched;
-  int64_t sched_len, next_step;
-  float* out;       // [8]
-};
-__global__ void __launch_bounds__(256) kv_finish_kernel(EvalFinish f) {
-  const float cur = f.sched ? f.sched[2 * max(int64_t(0), min(f.next_step - 1, f.sched_len - 1)) + 1] : 1.f;
-  float fph = 0.f, rec = 0.f, nw = cur;
-  if (f.cv) {
-    fph = f.cv[0] / f.hours_v;  // float32 division (x / 0 -> inf, 0 / 0 -> nan, as torch)
-    rec = f.n_pos_v > 0.f ? f.cv[3] / f.n_pos_v : 0.f;
-    if (f.ratio > 0.f) nw = fph > f.target ? cur * f.ratio : fmaxf(1.f, cur / f.ratio);
-  }
-  if (threadIdx.x == 0 && f.out) {
-    f.out[0] = fph;
-    f.out[1] = rec;
-    if (f.ct) {
-      f.out[2] = f.ct[0] / fmaxf(f.n_neg_t, 1.f);
-      f.out[3] = f.n_pos_t > 0.f ? f.ct[3] / f.n_pos_t : 0.f;
-      f.out[4] = (f.ct[3] + (f.n_neg_t - f.ct[1])) / fmaxf(f.n_neg_t + f.n_pos_t, 1.f);
-    } else {
-      f.out[2] = f.out[3] = f.out[4] = 0.f;
-    }
-    f.out[5] = nw;
-    f.out[6] = cur;
-    f.out[7] = 0.f;
-  }
-  if (f.cv && f.ratio > 0.f && f.sched)
-    for (int64_t s = f.next_step + threadIdx.x; s < f.sched_len; s += blockDim.x) f.sched[2 * s + 1] = nw;
-}
-
-// --------------------------------------------------------- workspace ------
-struct FusedWs {
-  int64_t wsplit, part, pstride, hg_part, xhat[2], U, Xn, dS, dHG, rinfo[2], mask[2], maxS, total;  // float offsets
-};
 // the weight cache's segments (WSplit) for plan p: W_o_k (k < NG - 1), then W_hg_k (k >= 1)
 WSplit make_wsplit(const hbk_mlp_plan& p) {
   const int NG = static_cast<int>(p.g.size());
@@ -3173,150 +2324,8 @@ WSplit make_wsplit(const hbk_mlp_plan& p) {
   for (int k = 1; k < NG; ++k) add(p.g[k].w_hg, 2 * p.g[k].hid, p.g[k].in);
   return w;
 }
-int64_t wsplit_halves(int NG) { return int64_t(NG - 1) * 4 * (kL * kH + kH2 * kL); }
-int k1_blocks(int B) { return ((B + kRB - 1) / kRB + 7) / 8 * 8; }  // row blocks, XCD-aware
-int k1_splits(int B) {  // (one round of three per CU on a 64-CU stream, KS 8, measured 92.1 vs 88.4 us per step)
-  static const int forced = getenv("HBK_K1_KS") ? atoi(getenv("HBK_K1_KS")) : 0;  // (A/B: 4 6 8 12 16 24)
-  if (forced == 4 || forced == 6 || forced == 8 || forced == 12 || forced == 16 || forced == 24) return forced;
-  static const int ks_opts[] = {4, 6, 8, 12, 16, 24};
-  for (int ks : ks_opts)
-    if (k1_blocks(B) * ks >= 256) return ks;
-  return 24;
-}
-// k3's batch splits: rows per split by the stream's width (see kK3Steps)
-int k3_rows(const void* stream) {
-  static const bool k3_wide = getenv("HBK_K3_WIDE") != nullptr;
-  const bool narrow = !k3_wide && persistent_blocks(1, stream) <= kK3NarrowCUs;
-  return 32 * (narrow ? kK3StepsNarrow * kK3GroupNarrow : kK3Steps);
-}
-FusedWs fused_layout(int64_t B, int NG, int64_t n_params = 0) {
-  FusedWs w;
-  int64_t o = 0;
-  auto take = [&](int64_t n) { const int64_t r = o; o += (n + 63) & ~int64_t(63); return r; };
-  const int64_t Bp = (B + kR - 1) / kR * kR;
-  w.wsplit = take(wsplit_halves(NG) / 2);  // first: its offset does not depend on B
-  // k3's partial slabs (the most splits either width takes), at a fixed offset too
-  w.pstride = (n_params + 63) & ~int64_t(63);
-  w.part = take(w.pstride * ((Bp + 32 * std::min(kK3StepsNarrow, kK3Steps) - 1) /
-                             (32 * std::min(kK3StepsNarrow, kK3Steps))));
-  w.hg_part = take(int64_t(24) * B * kH2);
-  w.xhat[0] = take(Bp * kD);
-  w.xhat[1] = take(Bp * kD);
-  // k3s reads these four unclamped, up to kK3sMaxR floats past an array's end (zeroed at use):
-  // each is followed by that many floats that nothing writes, whatever the order of the arrays
-  auto take_k3s = [&](int64_t n) { return take(n + kK3sMaxR); };
-  w.U = take_k3s(int64_t(NG) * Bp * kH);
-  w.Xn = take_k3s(int64_t(NG) * Bp * kL);
-  w.dS = take_k3s(int64_t(NG) * Bp * kL);
-  w.dHG = take_k3s(int64_t(NG) * Bp * kH2);
-  w.rinfo[0] = take(Bp * 4);
-  w.rinfo[1] = take(Bp * 4);
-  w.mask[0] = take(Bp * kMaskW);
-  w.mask[1] = take(Bp * kMaskW);
-  w.maxS = take(int64_t(2) * NG * (Bp / kR) * 4);
-  w.total = o;
-  return w;
-}
-
-// HBK_STEP=2: the v2 step (k1s -> k1c / k3s from the pool rows); 1: the k1a -> xhat^T ->
-// k1b / k3 path. By default the faster one as measured for the batch (tools/ab_step.sh, 64
-// CUs, r06: B = 1,100 v2 83.2 / v1 87.3 us; 550 65.1 / 63.5; 273 59.8 / 56.7; 138 57.2 /
-// 51.4 -- k3s's fixed prologue and its 2 splits at ceil(Bp / 128) slabs cost it the small
-// batches): v2 from kStepV2MinB rows (HBK_STEP_V2_MIN_B), on a stream of at most
-// kStepV2MaxCUs CUs -- on the whole GPU v1 is faster (B = 1,100: 59.1 against 66.1 us; its
-// 288-row splits and 32-column tiles spread over 256 CUs, where k3s's 256-column tiles and
-// fixed prologue do not)
-constexpr int kStepV2MinB = 800, kStepV2MaxCUs = 128;
-bool step_v2(int64_t B, const void* stream) {
-  static const int forced = getenv("HBK_STEP") ? atoi(getenv("HBK_STEP")) : 0;
-  static const int min_b = getenv("HBK_STEP_V2_MIN_B") ? atoi(getenv("HBK_STEP_V2_MIN_B")) : kStepV2MinB;
-  if (forced) return forced == 2;
-  return B >= min_b && persistent_blocks(1, stream) <= kStepV2MaxCUs;
-}
-int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
-// k1c's geometry: K chunk KC (KS = 1536 / KC chunks) and row tiles RT per block, by a
-// per-CU byte model: the block's pool rows (~2.2 B per element at the training mix),
-// its W slice and its partial slab, times the rounds of blocks per CU, plus the KS
-// slabs each k2 row tile sums first (HBK_K1_KC / HBK_K1_RT override)
-struct K1cGeom {
-  int KC, RT, KS, blocks;
-};
-int k1c_rtmax(int KC) {
-  switch (KC) {
-    case 64: return k1c_rt_max<64>();
-    case 96: return k1c_rt_max<96>();
-    case 192: return k1c_rt_max<192>();
-    default: return k1c_rt_max<384>();
-  }
-}
-K1cGeom k1c_geom(int B, const void* stream) {
-  const int cus = static_cast<int>(std::max<int64_t>(1, persistent_blocks(1, stream)));
-  const int fkc = env_int("HBK_K1_KC", 0), frt = env_int("HBK_K1_RT", 0);
-  K1cGeom best{192, 9, 8, 0};
-  double best_cost = 1e30;
-  for (int KC : {64, 96, 192, 384}) {
-    if (fkc && KC != fkc) continue;
-    const int rtm = k1c_rtmax(KC);
-    const double lds = 16.0 * rtm * (KC + 16) * 4 + 8.0 * KC;
-    const int per_cu = std::max(1, std::min(2, static_cast<int>(160.0 * 1024 / lds)));
-    for (int RT = 1; RT <= rtm; ++RT) {
-      if (frt && RT != std::min(frt, rtm)) continue;
-      const int KS = kD / KC, nrb = (B + 16 * RT - 1) / (16 * RT), blocks = nrb * KS;
-      const int rounds = (blocks + cus * per_cu - 1) / (cus * per_cu);
-      const int on_cu = std::min(per_cu, (blocks + cus - 1) / cus);
-      const double rows = std::min(16 * RT, B);
-      const double per_wg = rows * KC * 2.2 + 128.0 * KC * 4 + rows * 128 * 4;
-      const double cost = per_wg * on_cu * rounds + KS * 16.0 * 128 * 4;
-      if (cost < best_cost) {
-        best_cost = cost;
-        best = K1cGeom{KC, RT, KS, blocks};
-      }
-    }
-  }
-  return best;
-}
-// k3s's batch splits: the input layer's job (12 of the launch's tiles and the bulk of its
-// FLOPs) gets S0 splits of NST0 32-row steps, the small generic jobs S1 <= S0 of NST1, so
-// that the launch fits the CUs in one round and its longest workgroup (steps x the job's
-// relative step cost: the generic tiles have 4 or 6 of 8 column tiles live) is shortest.
-// The step counts are compile-time (fully unrolled steps), one of kK3sPairs; at most
-// ceil(Bp / 128) splits (the workspace's slabs). HBK_K3_R forces one pair by its rows.
-constexpr int kK3sPairs[][2] = {{1, 1}, {2, 2}, {3, 3}, {3, 5}, {4, 4}, {4, 9}, {4, 12}, {5, 12},
-                                {6, 14}, {7, 16}, {8, 8}, {9, 16}, {12, 12}, {16, 16}};
-constexpr int kK3sNPairs = sizeof(kK3sPairs) / sizeof(kK3sPairs[0]);
 constexpr int k3s_occ(int) { return 2; }  // (two workgroups per CU measured no faster: the
                                           // CU's load rate binds, r06)
-struct K3sPlan {
-  int S0, S1, pair;
-};
-// per-workgroup time model (units of ~0.78 us, the generic jobs' 32-row step of r06, fitted
-// to the traced spans): the input layer's 3 + 1.6 x steps, a generic job's 2.5 + 0.65 x steps
-K3sPlan k3s_plan(int64_t Bp, int tiles0, int tiles1, const void* stream) {
-  const int cus = static_cast<int>(std::max<int64_t>(1, persistent_blocks(1, stream)));
-  const int64_t max_s = (Bp + 127) / 128;
-  const int fr = env_int("HBK_K3_R", 0), fq = env_int("HBK_K3_PAIR", -1);
-  auto splits = [&](int st) { return static_cast<int>((Bp + 32 * st - 1) / (32 * st)); };
-  K3sPlan best{splits(16), splits(16), kK3sNPairs - 1};
-  double best_cost = 1e30;
-  for (int q = 0; q < kK3sNPairs; ++q) {
-    const int st0 = kK3sPairs[q][0], st1 = kK3sPairs[q][1];
-    if (fr > 0 && 32 * st0 < fr) continue;
-    if (fq >= 0 && q != fq) continue;
-    const int s0 = splits(st0), s1 = splits(st1);
-    if (s0 > max_s && st0 < 16) continue;  // (the workspace's slabs)
-    const int wgs = tiles0 * s0 + tiles1 * s1, rounds = (wgs + cus - 1) / cus;
-    const double cost = rounds * std::max(3.0 + 1.6 * st0, 2.5 + 0.65 * st1) + 1e-3 * wgs;
-    if (cost < best_cost) {
-      best_cost = cost;
-      best = K3sPlan{s0, s1, q};
-    }
-    if (fr > 0) break;
-  }
-  return best;
-}
 template <int Q = 0>
 void launch_k3s(int q, dim3 grid, hipStream_t s, const K3sArgs& k3) {
   if constexpr (Q < kK3sNPairs) {
@@ -3327,7 +2336,8 @@ void launch_k3s(int q, dim3 grid, hipStream_t s, const K3sArgs& k3) {
   }
 }
 
-void fill_k2(const hbk_mlp_plan& p, K2Args& k) {
+// k2's parameter offsets, and the weight cache's planes as it reads them
+void fill_k2(const hbk_mlp_plan& p, const _Float16* wc, K2Args& k) {
   const int NG = static_cast<int>(p.g.size());
   k.NG = NG;
   for (int i = 0; i < NG; ++i) {
@@ -3340,19 +2350,13 @@ void fill_k2(const hbk_mlp_plan& p, K2Args& k) {
     k.ln_g[i] = p.ln[i].g;
     k.ln_b[i] = p.ln[i].b;
   }
-}
-
-// the weight cache's plane offsets as k2 reads them
-void set_k2_cache(const WSplit& wsp, int NG, const _Float16* wc, K2Args& k2) {
-  k2.wc = wc;
-  for (int k = 0; k < NG; ++k) k2.c_o[k] = k2.c_oT[k] = k2.c_hg[k] = k2.c_hgT[k] = 0;
-  for (int sg = 0; sg < wsp.n; ++sg) {
-    const WSeg& g = wsp.s[sg];
-    const int64_t rc = int64_t(g.rows) * g.cols;
-    const bool is_o = sg < NG - 1;
-    const int k = is_o ? sg : sg - (NG - 1) + 1;
-    (is_o ? k2.c_o : k2.c_hg)[k] = g.dst;
-    (is_o ? k2.c_oT : k2.c_hgT)[k] = g.dst + 2 * rc;
+  k.wc = wc;
+  const WCacheOffsets c = mlp_wcache_offsets(p);
+  for (int i = 0; i < kMaxG; ++i) {
+    k.c_o[i] = c.c_o[i];
+    k.c_oT[i] = c.c_oT[i];
+    k.c_hg[i] = c.c_hg[i];
+    k.c_hgT[i] = c.c_hgT[i];
   }
 }
 
@@ -3372,37 +2376,6 @@ Ranges make_ranges(const hbk_mlp_plan& p) {
   return r;
 }
 
-// evaluation workspace: the weight cache (as the fused layout's first region),
-// W' planes, c0, c1
-struct EvalWs {
-  int64_t wsplit, wq, c0, c1, total;  // float offsets
-};
-EvalWs eval_layout(int NG) {
-  EvalWs w;
-  int64_t o = 0;
-  auto take = [&](int64_t n) { const int64_t r = o; o += (n + 63) & ~int64_t(63); return r; };
-  w.wsplit = take(wsplit_halves(NG) / 2);
-  w.wq = take(int64_t(kH2) * kD);  // 2 planes of halves
-  w.c0 = take(kH2);
-  w.c1 = take(kH2);
-  w.total = o;
-  return w;
-}
-
-}  // namespace
-
-bool mlp_fused_supported(const hbk_mlp_plan& p) {
-  return p.d_in == kD && p.layer == kL && p.hid == kH && static_cast<int>(p.g.size()) <= kMaxG &&
-         p.g.size() >= 2;
-}
-
-int64_t mlp_fused_ws_floats(const hbk_mlp_plan& p, int64_t B) {
-  return fused_layout(std::max<int64_t>(B, 1), static_cast<int>(p.g.size()), p.n_params).total;
-}
-
-int mlp_fused_step_variant(int64_t B, hipStream_t s) { return step_v2(B, s) ? 2 : 1; }
-
-// k1 + k2 (+ k3): the forward (inference) or forward/backward half of a step.
 #ifdef HBK_BOUNDS
 void bounds_set(std::initializer_list<std::pair<const void*, int64_t>> rs) {
   unsigned long long h[kBMax][2] = {};
@@ -3418,13 +2391,284 @@ void bounds_set(std::initializer_list<std::pair<const void*, int64_t>> rs) {
   (void)hipMemcpyToSymbol(HIP_SYMBOL(g_bn), &n, sizeof(n));
 }
 #endif
+
+// What the launches of one mlp_fused_run call share: the call's arguments, its plan, and the
+// row arguments (k1a / k1s, standalone or as k2's prefetch workgroups)
+struct StepRun {
+  const hbk_mlp_plan& p;
+  const StepPlan& pl;
+  const float* params;
+  const float* pool32;
+  const _Float16* pool16;
+  const float* y;
+  int64_t y_stride;
+  int B;
+  const float* state;
+  int parity;
+  const float* sched;
+  int sched_len;
+  float neg_weight, thr, act_thr, keep;
+  float* bucket;
+  float* prob;
+  float* logit;
+  float* ws;
+  bool train;
+  int flags;
+  hipStream_t s;
+  K1aArgs ka;
+};
+
+// rows: k1a (xhat^T) | k1s (statistics and mask) of this step
+int launch_rows(const StepRun& r) {
+  const bool v2 = r.pl.variant == 2;
+  void (*kern)(K1aArgs, int) = v2 ? (r.ka.idx ? k1s_kernel<true> : k1s_kernel<false>)
+                                  : (r.ka.idx ? k1a_kernel<true> : k1a_kernel<false>);
+  hipLaunchKernelGGL(kern, dim3(r.pl.rt), dim3(256), 0, r.s, r.ka, 0);
+  HBK_LAUNCH_CHECK(v2 ? "k1s_kernel" : "k1a_kernel");
+  return HBK_OK;
+}
+
+// input GEMM: k1b (from xhat^T) | k1c (from the pool rows) -> the KS partial slabs of HG0
+int launch_input_gemm(const StepRun& r) {
+  const hbk_mlp_plan& p = r.p;
+  const FusedWs& w = r.pl.ws;
+  float* stats = r.train ? r.bucket + p.n_params : nullptr;
+  if (r.pl.variant == 2) {
+    const K1cGeom& g1 = r.pl.k1c;
+    K1cArgs kc;
+    kc.P = r.params;
+    kc.g_in = p.ln_in.g;
+    kc.b_in = p.ln_in.b;
+    kc.w0 = p.g[0].w_hg;
+    kc.B = r.B;
+    kc.RT = g1.RT;
+    kc.KS = g1.KS;
+    kc.pool32 = r.pool32;
+    kc.pool16 = r.pool16;
+    kc.rinfo = r.ka.rinfo[r.parity];
+    kc.mask = r.ka.mask[r.parity];
+    kc.keep = r.keep;
+    kc.hg_part = r.ws + w.hg_part;
+    kc.stats = stats;
+    auto launch = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(r.pl.k1_grid), dim3(512), 0, r.s, kc); };
+    switch (g1.KC) {
+      case 64: launch(k1c_kernel<64>); break;
+      case 96: launch(k1c_kernel<96>); break;
+      case 192: launch(k1c_kernel<192>); break;
+      default: launch(k1c_kernel<384>);
+    }
+    HBK_LAUNCH_CHECK("k1c_kernel");
+    return HBK_OK;
+  }
+  K1bArgs kb;
+  kb.P = r.params;
+  kb.g_in = p.ln_in.g;
+  kb.b_in = p.ln_in.b;
+  kb.w0 = p.g[0].w_hg;
+  kb.B = r.B;
+  kb.xhat = r.ws + w.xhat[r.parity];
+  kb.Bp = r.pl.Bp;
+  kb.hg_part = r.ws + w.hg_part;
+  kb.stats = stats;
+  auto launch = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(r.pl.k1_grid), dim3(256), 0, r.s, kb); };
+  switch (r.pl.KS) {
+    case 4: launch(k1b_kernel<4>); break;
+    case 6: launch(k1b_kernel<6>); break;
+    case 8: launch(k1b_kernel<8>); break;
+    case 12: launch(k1b_kernel<12>); break;
+    case 16: launch(k1b_kernel<16>); break;
+    default: launch(k1b_kernel<24>);
+  }
+  HBK_LAUNCH_CHECK("k1b_kernel");
+  return HBK_OK;
+}
+
+template <bool kTrain>
+auto k2_kernel(int NG) {
+  return NG == 2 ? k2_rows_kernel<kTrain, 2> : NG == 3 ? k2_rows_kernel<kTrain, 3> : k2_rows_kernel<kTrain, 4>;
+}
+// k2: the rest of the network per row tile (and, as extra workgroups, the next step's rows)
+int launch_k2(const StepRun& r) {
+  const FusedWs& w = r.pl.ws;
+  const bool v2 = r.pl.variant == 2;
+  K2Args k2;
+  k2.P = r.params;
+  k2.B = r.B;
+  k2.KS = r.pl.KS;
+  fill_k2(r.p, reinterpret_cast<const _Float16*>(r.ws + w.wsplit), k2);
+  k2.hg_part = r.ws + w.hg_part;
+  k2.y = r.y;
+  k2.y_stride = r.y_stride;
+  k2.state = r.state;
+  k2.parity = r.parity;
+  k2.sched = r.sched;
+  k2.sched_len = r.sched_len;
+  k2.neg_weight = r.neg_weight;
+  k2.thr = r.thr;
+  k2.act_thr = r.act_thr;
+  k2.prob = r.prob;
+  k2.logit = r.logit;
+  k2.counts = nullptr;
+  k2.count_label = 0;
+  k2.G = r.bucket;
+  k2.stats = r.bucket ? r.bucket + r.p.n_params : nullptr;
+  k2.U = r.ws + w.U;
+  k2.Xn = r.ws + w.Xn;
+  k2.dS = r.ws + w.dS;
+  k2.dHG = r.ws + w.dHG;
+  k2.Bp = r.pl.Bp;
+  k2.n_rt = r.pl.rt;
+  k2.prefetch = r.train && r.ka.idx && (r.flags & HBK_STEP_PREFETCH_NEXT);
+  k2.pre = r.ka;
+  k2.v2 = v2 ? 1 : 0;
+  k2.maxS = v2 && r.train ? r.ws + w.maxS : nullptr;
+  k2.pre_tiles = r.pl.pre_tiles;
+  const int grid = k2.prefetch ? r.pl.k2_grid_pre : r.pl.k2_grid;
+  void (*kern)(K2Args) = r.train ? k2_kernel<true>(k2.NG) : k2_kernel<false>(k2.NG);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * kK2Waves), 0, r.s, k2);  // (each wave publishes to maxS)
+  HBK_LAUNCH_CHECK("k2_rows_kernel");
+  return HBK_OK;
+}
+
+// What K3Args and K3sArgs share: the jobs' operands in the order of step_job (job 0 = the
+// input layer, whose activation is Y0: v1's xhat^T, or NULL for v2's pool rows; then dW_hg of
+// GMLPs 1 .., then dW_o of every GMLP), their starts, the input layer's post-op and the slabs
+template <typename Args>
+void fill_wgrad(const StepRun& r, const float* Y0, Args& k3) {
+  static_assert(sizeof(k3.job) / sizeof(k3.job[0]) == kMaxJobs && sizeof(k3.start) / sizeof(int) == kMaxJobs + 1,
+                "the job tables hold the plan's jobs");
+  const hbk_mlp_plan& p = r.p;
+  const FusedWs& w = r.pl.ws;
+  const int NG = static_cast<int>(p.g.size());
+  const int64_t Bp = r.pl.Bp;
+  for (int i = 0; i < r.pl.n_jobs; ++i) {
+    auto& j = k3.job[i];
+    const int k = i < NG ? i : i - NG;
+    if (i < NG) {
+      j.X = r.ws + w.dHG + int64_t(k) * kH2 * Bp;
+      j.Y = i ? r.ws + w.Xn + int64_t(k) * kL * Bp : Y0;
+      j.c_off = p.g[k].w_hg;
+    } else {
+      j.X = r.ws + w.dS + int64_t(k) * kL * Bp;
+      j.Y = r.ws + w.U + int64_t(k) * kH * Bp;
+      j.c_off = p.g[k].w_o;
+    }
+    const JobShape js = step_job(NG, i);
+    j.M = js.M;
+    j.N = j.ldc = js.N;
+    j.tn = r.pl.job_tn[i];
+  }
+  for (int i = 0; i <= r.pl.n_jobs; ++i) k3.start[i] = r.pl.job_start[i];
+  k3.n_jobs = r.pl.n_jobs;
+  k3.Bp = Bp;
+  k3.g_in = r.params + p.ln_in.g;
+  k3.b_in = r.params + p.ln_in.b;
+  k3.W0 = r.params + p.g[0].w_hg;
+  k3.g_off = p.ln_in.g;
+  k3.b_off = p.ln_in.b;
+  k3.part = r.ws + w.part;
+  k3.pstride = w.pstride;
+}
+
+// weight gradients: k3 | k3s, one partial slab per batch split
+int launch_wgrad(const StepRun& r) {
+  const StepPlan& pl = r.pl;
+  const dim3 grid(pl.job_start[pl.n_jobs]);
+  if (pl.variant == 2) {
+    K3sArgs k3;
+    fill_wgrad(r, nullptr, k3);
+    for (int i = 0; i < pl.n_jobs; ++i) {
+      k3.job[i].mat = i;  // k2's maxS index: dHG_k = k, dS_k = NG + k
+      k3.job[i].S = pl.job_splits[i];
+      k3.job[i].R = 32 * kK3sPairs[pl.k3s_pair][i == 0 ? 0 : 1];
+    }
+    k3.S = pl.slabs;
+    k3.n_rt = pl.rt;
+    k3.B = r.B;
+    k3.maxS = r.ws + pl.ws.maxS;
+    k3.pool32 = r.pool32;
+    k3.pool16 = r.pool16;
+    k3.rinfo = r.ka.rinfo[r.parity];
+    k3.mask = r.ka.mask[r.parity];
+    k3.keep = r.keep;
+    k3.sparse = pl.sparse;
+    launch_k3s(pl.k3s_pair, grid, r.s, k3);
+    HBK_LAUNCH_CHECK("k3s_kernel");
+    return HBK_OK;
+  }
+  K3Args k3;
+  fill_wgrad(r, r.ws + pl.ws.xhat[r.parity], k3);
+  k3.KS = pl.slabs;
+  if (pl.k3_narrow)
+    hipLaunchKernelGGL((k3_wgrad_kernel<kK3StepsNarrow, kK3GroupNarrow>), grid, dim3(256), 0, r.s, k3);
+  else
+    hipLaunchKernelGGL((k3_wgrad_kernel<kK3Steps, 1>), grid, dim3(256), 0, r.s, k3);
+  HBK_LAUNCH_CHECK("k3_wgrad_kernel");
+  return HBK_OK;
+}
+
+// the slabs: left for the update that gets this workspace, or added into the bucket now
+int finish_partials(const StepRun& r) {
+  if (r.flags & HBK_STEP_DEFER_PARTIALS) {
+    r.p.deferred_ws = r.ws;
+    r.p.deferred_ks = r.pl.slabs;
+    return HBK_OK;
+  }
+  r.p.deferred_ws = nullptr;
+  hipLaunchKernelGGL(k3_fold_kernel, dim3(unsigned(std::min<int64_t>((r.p.n_params / 4 + 255) / 256, 1024))), dim3(256),
+                     0, r.s, make_ranges(r.p), r.ws + r.pl.ws.part, r.pl.ws.pstride, r.pl.slabs, r.bucket, r.p.n_params);
+  HBK_LAUNCH_CHECK("k3_fold_kernel");
+  return HBK_OK;
+}
+
+}  // namespace
+
+bool mlp_fused_supported(const hbk_mlp_plan& p) {
+  return p.d_in == kD && p.layer == kL && p.hid == kH && static_cast<int>(p.g.size()) <= kMaxG &&
+         p.g.size() >= 2;
+}
+
+int64_t mlp_fused_ws_floats(const hbk_mlp_plan& p, int64_t B) {
+  return fused_layout(std::max<int64_t>(B, 1), static_cast<int>(p.g.size()), p.n_params).total;
+}
+
+int mlp_fused_step_variant(int64_t B, hipStream_t s) {
+  return step_v2(B, persistent_blocks(1, s), read_step_knobs()) ? 2 : 1;  // (plan_step's variant)
+}
+
+WCacheOffsets mlp_wcache_offsets(const hbk_mlp_plan& p) {
+  const int NG = static_cast<int>(p.g.size());
+  const WSplit wsp = make_wsplit(p);
+  WCacheOffsets c{};
+  for (int sg = 0; sg < wsp.n; ++sg) {
+    const WSeg& g = wsp.s[sg];
+    const int64_t rc = int64_t(g.rows) * g.cols;
+    const bool is_o = sg < NG - 1;
+    const int k = is_o ? sg : sg - (NG - 1) + 1;
+    (is_o ? c.c_o : c.c_hg)[k] = g.dst;
+    (is_o ? c.c_oT : c.c_hgT)[k] = g.dst + 2 * rc;
+  }
+  return c;
+}
+
+int mlp_wcache_fill(const hbk_mlp_plan& p, const float* params, float* cache, hipStream_t s) {
+  const int64_t n4 = wsplit_halves(static_cast<int>(p.g.size())) / 16;  // float4s of the segments
+  hipLaunchKernelGGL(k0_wsplit_kernel, dim3(unsigned(std::min<int64_t>((n4 + 255) / 256, 256))), dim3(256), 0, s,
+                     make_wsplit(p), params, reinterpret_cast<_Float16*>(cache), n4);
+  HBK_LAUNCH_CHECK("k0_wsplit_kernel");
+  return HBK_OK;
+}
+
+// The forward (inference) or forward / backward half of a step: one plan, then one launch per stage.
 int mlp_fused_run(const hbk_mlp_plan& p, const float* params, const float* pool32, int64_t n32,
                   const void* pool16, int64_t n16, const int32_t* idx, int64_t idx_stride, int64_t idx_steps,
                   const float* y, int64_t y_stride, int B, const float* state, int parity, const float* sched,
                   int sched_len, float neg_weight, float thr, float act_thr, float drop_p, uint64_t seed,
                   float* bucket, float* prob, float* logit, float* ws, bool train, int flags, hipStream_t s) {
-  const int NG = static_cast<int>(p.g.size());
-  const FusedWs w = fused_layout(B, NG, p.n_params);
+  const StepKnobs kn = read_step_knobs();
+  const int64_t cus = persistent_blocks(1, s);
+  const StepPlan pl = plan_step(B, static_cast<int>(p.g.size()), p.n_params, cus, kn);
+  const FusedWs& w = pl.ws;
 #ifdef HBK_BOUNDS
   bounds_set({{params, p.n_params * 4},
               {pool32, n32 * kD * 4},
@@ -3438,12 +2682,21 @@ int mlp_fused_run(const hbk_mlp_plan& p, const float* params, const float* pool3
               {logit, int64_t(B) * 4},
               {ws, w.total * 4}});
 #endif
-
-  const int64_t Bp = (B + kR - 1) / kR * kR;
-  const int rt = (B + kR - 1) / kR;
-  K1aArgs ka;
+  if (kn.plan_log && train && pl.variant == 2) {  // (tuning aid) the plan of each distinct batch, once
+    static int64_t logged = -1;
+    if (logged != pl.Bp) {
+      logged = pl.Bp;
+      fprintf(stderr, "hbk k3s plan: Bp %lld, CUs %lld, S0 %d x %d steps, S1 %d x %d steps\n",
+              static_cast<long long>(pl.Bp), static_cast<long long>(cus), pl.S0, kK3sPairs[pl.k3s_pair][0], pl.S1,
+              kK3sPairs[pl.k3s_pair][1]);
+    }
+  }
+  const float keep = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
+  StepRun r{p, pl, params, pool32, static_cast<const _Float16*>(pool16), y, y_stride, B, state, parity, sched,
+            sched_len, neg_weight, thr, act_thr, keep, bucket, prob, logit, ws, train, flags, s, K1aArgs{}};
+  K1aArgs& ka = r.ka;
   ka.pool32 = pool32;
-  ka.pool16 = static_cast<const _Float16*>(pool16);
+  ka.pool16 = r.pool16;
   ka.n32 = pool32 ? n32 : 0;
   ka.n16 = pool16 ? n16 : 0;
   ka.idx = idx;
@@ -3454,269 +2707,22 @@ int mlp_fused_run(const hbk_mlp_plan& p, const float* params, const float* pool3
   ka.B = B;
   ka.drop_p = drop_p;
   ka.seed = seed;
-  ka.xhat[0] = ws + w.xhat[0];
-  ka.xhat[1] = ws + w.xhat[1];
-  ka.Bp = Bp;
+  ka.Bp = pl.Bp;
   for (int i = 0; i < 2; ++i) {
+    ka.xhat[i] = ws + w.xhat[i];
     ka.rinfo[i] = reinterpret_cast<uint4*>(ws + w.rinfo[i]);
     ka.mask[i] = reinterpret_cast<uint32_t*>(ws + w.mask[i]);
   }
-  const bool v2 = step_v2(B, s);
-  const float keep = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
-  const float* xhat = ws + w.xhat[parity];
-  const WSplit wsp = make_wsplit(p);
-  _Float16* wc = reinterpret_cast<_Float16*>(ws + w.wsplit);
-  if (!(flags & HBK_STEP_WEIGHTS_READY)) {  // the previous step's k4 did not leave the cache current
-    const int64_t n4 = wsplit_halves(NG) / 16;  // float4s of the segments
-    hipLaunchKernelGGL(k0_wsplit_kernel, dim3(unsigned(std::min<int64_t>((n4 + 255) / 256, 256))), dim3(256), 0,
-                       s, wsp, params, wc, n4);
-    HBK_LAUNCH_CHECK("k0_wsplit_kernel");
-  }
-  if (!(flags & HBK_STEP_XHAT_READY)) {  // this step's rows were not prefetched by the previous step
-    if (v2) {
-      if (idx)
-        hipLaunchKernelGGL(k1s_kernel<true>, dim3(rt), dim3(256), 0, s, ka, 0);
-      else
-        hipLaunchKernelGGL(k1s_kernel<false>, dim3(rt), dim3(256), 0, s, ka, 0);
-      HBK_LAUNCH_CHECK("k1s_kernel");
-    } else {
-      if (idx)
-        hipLaunchKernelGGL(k1a_kernel<true>, dim3(rt), dim3(256), 0, s, ka, 0);
-      else
-        hipLaunchKernelGGL(k1a_kernel<false>, dim3(rt), dim3(256), 0, s, ka, 0);
-      HBK_LAUNCH_CHECK("k1a_kernel");
-    }
-  }
-  int KS = k1_splits(B);
-  if (v2) {
-    const K1cGeom g1 = k1c_geom(B, s);
-    KS = g1.KS;
-    K1cArgs kc;
-    kc.P = params;
-    kc.g_in = p.ln_in.g;
-    kc.b_in = p.ln_in.b;
-    kc.w0 = p.g[0].w_hg;
-    kc.B = B;
-    kc.RT = g1.RT;
-    kc.KS = g1.KS;
-    kc.pool32 = pool32;
-    kc.pool16 = static_cast<const _Float16*>(pool16);
-    kc.rinfo = ka.rinfo[parity];
-    kc.mask = ka.mask[parity];
-    kc.keep = keep;
-    kc.hg_part = ws + w.hg_part;
-    kc.stats = train ? bucket + p.n_params : nullptr;
-    auto launch = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(g1.blocks), dim3(512), 0, s, kc); };
-    switch (g1.KC) {
-      case 64: launch(k1c_kernel<64>); break;
-      case 96: launch(k1c_kernel<96>); break;
-      case 192: launch(k1c_kernel<192>); break;
-      default: launch(k1c_kernel<384>);
-    }
-    HBK_LAUNCH_CHECK("k1c_kernel");
-  } else {
-  K1bArgs kb;
-  kb.P = params;
-  kb.g_in = p.ln_in.g;
-  kb.b_in = p.ln_in.b;
-  kb.w0 = p.g[0].w_hg;
-  kb.B = B;
-  kb.xhat = xhat;
-  kb.Bp = Bp;
-  kb.hg_part = ws + w.hg_part;
-  kb.stats = train ? bucket + p.n_params : nullptr;
-  {
-    auto launch = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(k1_blocks(B) * KS), dim3(256), 0, s, kb); };
-    switch (KS) {
-      case 4: launch(k1b_kernel<4>); break;
-      case 6: launch(k1b_kernel<6>); break;
-      case 8: launch(k1b_kernel<8>); break;
-      case 12: launch(k1b_kernel<12>); break;
-      case 16: launch(k1b_kernel<16>); break;
-      default: launch(k1b_kernel<24>);
-    }
-    HBK_LAUNCH_CHECK("k1b_kernel");
-  }
-  }
-  K2Args k2;
-  k2.P = params;
-  k2.B = B;
-  k2.KS = KS;
-  fill_k2(p, k2);
-  k2.hg_part = ws + w.hg_part;
-  k2.y = y;
-  k2.y_stride = y_stride;
-  k2.state = state;
-  k2.parity = parity;
-  k2.sched = sched;
-  k2.sched_len = sched_len;
-  k2.neg_weight = neg_weight;
-  k2.thr = thr;
-  k2.act_thr = act_thr;
-  k2.prob = prob;
-  k2.logit = logit;
-  k2.counts = nullptr;
-  k2.count_label = 0;
-  k2.G = bucket;
-  k2.stats = bucket ? bucket + p.n_params : nullptr;
-  k2.U = ws + w.U;
-  k2.Xn = ws + w.Xn;
-  k2.dS = ws + w.dS;
-  k2.dHG = ws + w.dHG;
-  k2.Bp = Bp;
-  k2.n_rt = rt;
-  k2.prefetch = train && idx && (flags & HBK_STEP_PREFETCH_NEXT);
-  k2.pre = ka;
-  k2.v2 = v2 ? 1 : 0;
-  k2.maxS = v2 && train ? ws + w.maxS : nullptr;
-  set_k2_cache(wsp, NG, wc, k2);
-  {
-    k2.pre_tiles = std::max(1, env_int("HBK_PRE_TILES", kPreTiles2));
-    const int pt = v2 ? k2.pre_tiles : kPreTiles;
-    const int grid = k2.prefetch ? rt + (rt + pt - 1) / pt : rt;
-    auto launch = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, k2); };
-    if (train) {
-      if (NG == 2) launch(k2_rows_kernel<true, 2>);
-      else if (NG == 3) launch(k2_rows_kernel<true, 3>);
-      else launch(k2_rows_kernel<true, 4>);
-    } else {
-      if (NG == 2) launch(k2_rows_kernel<false, 2>);
-      else if (NG == 3) launch(k2_rows_kernel<false, 3>);
-      else launch(k2_rows_kernel<false, 4>);
-    }
-    HBK_LAUNCH_CHECK("k2_rows_kernel");
-  }
-  if (!train) return HBK_OK;
-  if (v2) {  // k3s: job 0 = input layer (pool rows), then dW_hg of GMLPs 1.., then dW_o of every GMLP
-    constexpr int kNtRaw = 16 * kK3sNbtRaw, kNtGen = 16 * kK3sNbtGen;
-    K3sArgs k3;
-    int nj = 0, tiles = 0;
-    auto add = [&](const float* X, const float* Y, int64_t c_off, int ldc, int M, int N, int mat) {
-      K3sJob& j = k3.job[nj];
-      j.X = X;
-      j.Y = Y;
-      j.c_off = c_off;
-      j.ldc = ldc;
-      j.M = M;
-      j.N = N;
-      const int nt = Y ? kNtGen : kNtRaw;
-      j.tn = (N + nt - 1) / nt;
-      j.mat = mat;
-      k3.start[nj] = ((M + 127) / 128) * j.tn;  // (tiles; scaled by the job's splits below)
-      tiles += k3.start[nj];
-      ++nj;
-    };
-    add(ws + w.dHG, nullptr, p.g[0].w_hg, kD, kH2, kD, 0);
-    for (int k = 1; k < NG; ++k)
-      add(ws + w.dHG + int64_t(k) * kH2 * Bp, ws + w.Xn + int64_t(k) * kL * Bp, p.g[k].w_hg, kL, kH2, kL, k);
-    for (int k = 0; k < NG; ++k)
-      add(ws + w.dS + int64_t(k) * kL * Bp, ws + w.U + int64_t(k) * kH * Bp, p.g[k].w_o, kH, p.g[k].out, kH, NG + k);
-    const K3sPlan pl = k3s_plan(Bp, k3.start[0], tiles - k3.start[0], s);
-    const int S = pl.S0;
-    if (getenv("HBK_PLAN_LOG")) {  // (tuning aid) the plan of each distinct batch, once
-      static int64_t logged = -1;
-      if (logged != Bp) {
-        logged = Bp;
-        fprintf(stderr, "hbk k3s plan: Bp %lld, CUs %lld, S0 %d x %d steps, S1 %d x %d steps\n",
-                static_cast<long long>(Bp), static_cast<long long>(persistent_blocks(1, s)), pl.S0,
-                kK3sPairs[pl.pair][0], pl.S1, kK3sPairs[pl.pair][1]);
-      }
-    }
-    int wgs = 0;
-    for (int i = 0; i < nj; ++i) {
-      k3.job[i].S = i == 0 ? pl.S0 : pl.S1;
-      k3.job[i].R = 32 * kK3sPairs[pl.pair][i == 0 ? 0 : 1];
-      const int t = k3.start[i];
-      k3.start[i] = wgs;
-      wgs += t * k3.job[i].S;
-    }
-    k3.start[nj] = wgs;
-    k3.n_jobs = nj;
-    k3.S = S;
-    k3.n_rt = rt;
-    k3.B = B;
-    k3.Bp = Bp;
-    k3.maxS = ws + w.maxS;
-    k3.pool32 = pool32;
-    k3.pool16 = static_cast<const _Float16*>(pool16);
-    k3.rinfo = ka.rinfo[parity];
-    k3.mask = ka.mask[parity];
-    k3.keep = keep;
-    k3.g_in = params + p.ln_in.g;
-    k3.b_in = params + p.ln_in.b;
-    k3.W0 = params + p.g[0].w_hg;
-    k3.g_off = p.ln_in.g;
-    k3.b_off = p.ln_in.b;
-    k3.part = ws + w.part;
-    k3.pstride = w.pstride;
-    // HBK_STEP_DENSE=1 (A/B runs): every row tile is walked, as before the live-tile list
-    static const bool dense = env_int("HBK_STEP_DENSE", 0) != 0;
-    k3.sparse = !dense && rt <= kK3sMaxTiles ? 1 : 0;
-    launch_k3s(pl.pair, dim3(wgs), s, k3);
-    HBK_LAUNCH_CHECK("k3s_kernel");
-    if (flags & HBK_STEP_DEFER_PARTIALS) {
-      p.deferred_ws = ws;
-      p.deferred_ks = S;
-    } else {
-      p.deferred_ws = nullptr;
-      hipLaunchKernelGGL(k3_fold_kernel, dim3(unsigned(std::min<int64_t>((p.n_params / 4 + 255) / 256, 1024))), dim3(256),
-                         0, s, make_ranges(p), ws + w.part, w.pstride, S, bucket, p.n_params);
-      HBK_LAUNCH_CHECK("k3_fold_kernel");
-    }
-    return HBK_OK;
-  }
-  // k3: job 0 = input layer, then dW_hg of GMLPs 1.., then dW_o of every GMLP
-  K3Args k3;
-  int nj = 0, blocks = 0;
-  // HBK_K3_WIDE=1: the 288-row splits on narrow streams too (4 instead of 9
-  // splits at B = 1100: fewer partial slabs, more time on a small partition)
-  const int rows3 = k3_rows(s);
-  const bool narrow = rows3 == 32 * kK3StepsNarrow * kK3GroupNarrow;
-  const int KS3 = static_cast<int>((Bp + rows3 - 1) / rows3);
-  auto add = [&](const float* X, const float* Y, int64_t c_off, int ldc, int M, int N) {
-    WJob& j = k3.job[nj];
-    j.X = X;
-    j.Y = Y;
-    j.c_off = c_off;
-    j.ldc = ldc;
-    j.M = M;
-    j.N = N;
-    j.tn = (N + kTN - 1) / kTN;
-    k3.start[nj] = blocks;
-    blocks += ((M + kTM - 1) / kTM) * j.tn * KS3;
-    ++nj;
-  };
-  add(ws + w.dHG, xhat, p.g[0].w_hg, kD, kH2, kD);
-  for (int k = 1; k < NG; ++k)
-    add(ws + w.dHG + int64_t(k) * kH2 * Bp, ws + w.Xn + int64_t(k) * kL * Bp, p.g[k].w_hg, kL, kH2, kL);
-  for (int k = 0; k < NG; ++k)
-    add(ws + w.dS + int64_t(k) * kL * Bp, ws + w.U + int64_t(k) * kH * Bp, p.g[k].w_o, kH, p.g[k].out, kH);
-  k3.start[nj] = blocks;
-  k3.n_jobs = nj;
-  k3.KS = KS3;
-  k3.Bp = Bp;
-  k3.g_in = params + p.ln_in.g;
-  k3.b_in = params + p.ln_in.b;
-  k3.W0 = params + p.g[0].w_hg;
-  k3.g_off = p.ln_in.g;
-  k3.b_off = p.ln_in.b;
-  k3.part = ws + w.part;
-  k3.pstride = w.pstride;
-  if (narrow)
-    hipLaunchKernelGGL((k3_wgrad_kernel<kK3StepsNarrow, kK3GroupNarrow>), dim3(blocks), dim3(256), 0, s, k3);
-  else
-    hipLaunchKernelGGL((k3_wgrad_kernel<kK3Steps, 1>), dim3(blocks), dim3(256), 0, s, k3);
-  HBK_LAUNCH_CHECK("k3_wgrad_kernel");
-  if (flags & HBK_STEP_DEFER_PARTIALS) {  // the update adds the slabs
-    p.deferred_ws = ws;
-    p.deferred_ks = KS3;
-  } else {
-    p.deferred_ws = nullptr;
-    hipLaunchKernelGGL(k3_fold_kernel, dim3(unsigned(std::min<int64_t>((p.n_params / 4 + 255) / 256, 1024))), dim3(256),
-                       0, s, make_ranges(p), ws + w.part, w.pstride, KS3, bucket, p.n_params);
-    HBK_LAUNCH_CHECK("k3_fold_kernel");
-  }
-  return HBK_OK;
+  int rc = HBK_OK;
+  // the weight cache, unless the previous step's k4 left it current
+  if (!(flags & HBK_STEP_WEIGHTS_READY)) rc = mlp_wcache_fill(p, params, ws + w.wsplit, s);
+  // this step's rows, unless the previous step prefetched them
+  if (rc == HBK_OK && !(flags & HBK_STEP_XHAT_READY)) rc = launch_rows(r);
+  if (rc == HBK_OK) rc = launch_input_gemm(r);
+  if (rc == HBK_OK) rc = launch_k2(r);
+  if (rc != HBK_OK || !train) return rc;
+  rc = launch_wgrad(r);
+  return rc == HBK_OK ? finish_partials(r) : rc;
 }
 
 int mlp_fused_update(const hbk_mlp_plan& p, float* params, float* bucket, float* m, float* v, float* state,
@@ -3729,7 +2735,7 @@ int mlp_fused_update(const hbk_mlp_plan& p, float* params, float* bucket, float*
   }
   K4Args k;
   k.w = make_wsplit(p);
-  const FusedWs fl = fused_layout(1, static_cast<int>(p.g.size()), p.n_params);
+  const FusedFixed fl = fused_fixed(static_cast<int>(p.g.size()), p.n_params);  // (whatever the step's B was)
   k.wc = ws ? reinterpret_cast<_Float16*>(ws + fl.wsplit) : nullptr;
   k.part = p.deferred_ws ? ws + fl.part : nullptr;
   k.pstride = fl.pstride;
@@ -3775,176 +2781,6 @@ int mlp_fused_update(const hbk_mlp_plan& p, float* params, float* bucket, float*
   const int64_t blocks = (k.wc ? k.n_tiles : 0) + std::min<int64_t>((p.n_params / 4 + 255) / 256, 1024);
   hipLaunchKernelGGL(k4_update_kernel, dim3(unsigned(blocks)), dim3(256), 0, s, k);
   HBK_LAUNCH_CHECK("k4_update_kernel");
-  return HBK_OK;
-}
-
-int64_t mlp_eval_ws_floats(const hbk_mlp_plan& p, int64_t rows) {
-  (void)rows;  // the passes need no per-row workspace
-  return eval_layout(static_cast<int>(p.g.size())).total;
-}
-
-int mlp_eval_prepare(const hbk_mlp_plan& p, const float* params, float* ws, hipStream_t s) {
-  const int NG = static_cast<int>(p.g.size());
-  const EvalWs w = eval_layout(NG);
-  const WSplit wsp = make_wsplit(p);
-  const int64_t n4 = wsplit_halves(NG) / 16;
-  hipLaunchKernelGGL(k0_wsplit_kernel, dim3(unsigned(std::min<int64_t>((n4 + 255) / 256, 256))), dim3(256), 0, s,
-                     wsp, params, reinterpret_cast<_Float16*>(ws + w.wsplit), n4);
-  HBK_LAUNCH_CHECK("k0_wsplit_kernel");
-  hipLaunchKernelGGL(kv_prep_kernel, dim3(kH2), dim3(256), 0, s, params, p.g[0].w_hg, p.ln_in.g, p.ln_in.b,
-                     reinterpret_cast<_Float16*>(ws + w.wq), ws + w.c0, ws + w.c1);
-  HBK_LAUNCH_CHECK("kv_prep_kernel");
-  return HBK_OK;
-}
-
-// How a single-pool pass of `rows` row evaluations is launched: part[0] rows in the lap form (whole sets
-// of two laps, so no set carries a dead lap), part[1] in the plain form. Laps are for f16 pools read in
-// order that the pass covers at least twice. HBK_EVAL_LAPS=0 (read per call, so one process can compare)
-// restores the plain form everywhere.
-void mlp_eval_lap_plan(int64_t rows, int64_t n_pool, bool f16, bool has_idx, int64_t part[2]) {
-  part[0] = 0;
-  part[1] = rows;
-  const char* e = getenv("HBK_EVAL_LAPS");
-  if ((e && e[0] == '0') || !f16 || has_idx || n_pool <= 0 || rows <= 0) return;
-  part[0] = rows / (2 * n_pool) * (2 * n_pool);
-  part[1] = rows - part[0];
-}
-
-// One kv_gemm_kernel launch over nseg pools of one dtype (nseg = 1: the single-pool fields,
-// which also allow idx / prob; nseg > 1: the segment table, workgroups in pool order).
-static int mlp_eval_launch(const hbk_mlp_plan& p, const float* params, bool f16, const EvalSeg* seg, int nseg,
-                           const int32_t* idx, float act_thr, float drop_p, float* prob, float* ws, hipStream_t s) {
-  const int NG = static_cast<int>(p.g.size());
-  const EvalWs w = eval_layout(NG);
-  const WSplit wsp = make_wsplit(p);
-  K2Args kc{};  // the weight cache's plane offsets as k2 reads them
-  set_k2_cache(wsp, NG, reinterpret_cast<const _Float16*>(ws + w.wsplit), kc);
-  KvArgs ka{};
-  ka.pool = seg[0].pool;
-  ka.n_pool = seg[0].n_pool;
-  ka.idx = idx;
-  ka.rows = seg[0].rows;
-  ka.r0 = seg[0].r0;
-  ka.wq = reinterpret_cast<const _Float16*>(ws + w.wq);
-  ka.c0 = ws + w.c0;
-  ka.c1 = ws + w.c1;
-  ka.drop_p = drop_p;
-  ka.seed = seg[0].seed;
-  ka.P = params;
-  for (int i = 0; i < kMaxG; ++i) {
-    const int g = std::min(i, NG - 1);
-    ka.b_hg[i] = p.g[g].b_hg;
-    ka.b_o[i] = p.g[g].b_o;
-    ka.w_o[i] = p.g[g].w_o;
-    ka.ln_g[i] = i + 1 < NG ? p.ln[i].g : 0;
-    ka.ln_b[i] = i + 1 < NG ? p.ln[i].b : 0;
-    ka.c_o[i] = kc.c_o[i];
-    ka.c_hg[i] = kc.c_hg[i];
-  }
-  ka.wc = kc.wc;
-  ka.act_thr = act_thr;
-  ka.counts = seg[0].counts;
-  ka.label = seg[0].label;
-  ka.prob = prob;
-  // f16 rows: 16 waves of one 16-row tile each (126 VGPRs); f32 rows (the split's registers
-  // spill at 128): 8 waves. HBK_KV_WAVES=8: 8 waves of two tiles for f16 rows too (A/B)
-  static const bool w8 = getenv("HBK_KV_WAVES") && atoi(getenv("HBK_KV_WAVES")) == 8;
-  const int waves = f16 && !w8 ? 16 : 8;
-  const int tile = (f16 ? 256 : 128);  // kv_gemm_kernel's rows per workgroup
-  int64_t tiles = (seg[0].rows + tile - 1) / tile;
-  ka.nseg = 0;
-  if (nseg > 1) {
-    ka.nseg = nseg;
-    tiles = 0;
-    for (int i = 0; i < nseg; ++i) {
-      ka.seg_tile0[i] = static_cast<int>(tiles);
-      ka.seg_pool[i] = seg[i].pool;
-      ka.seg_npool[i] = seg[i].n_pool;
-      ka.seg_rows[i] = seg[i].rows;
-      ka.seg_r0[i] = seg[i].r0;
-      ka.seg_seed[i] = seg[i].seed;
-      ka.seg_counts[i] = seg[i].counts;
-      ka.seg_label[i] = seg[i].label;
-      tiles += (seg[i].rows + tile - 1) / tile;
-    }
-    ka.seg_tile0[nseg] = static_cast<int>(tiles);
-  }
-  // the lap form first, over the pass's whole lap sets; what is left goes to the plain form
-  if (nseg == 1) {
-    int64_t part[2];
-    mlp_eval_lap_plan(seg[0].rows, seg[0].n_pool, f16, idx != nullptr, part);
-    if (part[0] > 0) {
-      ka.lap_tiles = static_cast<int>((seg[0].n_pool + 127) / 128);
-      ka.rows = part[0];
-      const dim3 lgrid(static_cast<unsigned>(part[0] / (2 * seg[0].n_pool) * ka.lap_tiles));
-      auto llaunch = [&](auto kern) { hipLaunchKernelGGL(kern, lgrid, dim3(512), 0, s, ka); };
-      if (NG == 2) llaunch(kv_gemm_kernel<true, 2, 8, 2>);
-      else if (NG == 3) llaunch(kv_gemm_kernel<true, 3, 8, 2>);
-      else llaunch(kv_gemm_kernel<true, 4, 8, 2>);
-      HBK_LAUNCH_CHECK("kv_gemm_kernel (laps)");
-      ka.r0 += part[0];
-      if (ka.prob) ka.prob += part[0];
-      ka.lap_tiles = 0;
-      ka.rows = part[1];
-      if (part[1] == 0) return HBK_OK;
-      tiles = (part[1] + tile - 1) / tile;
-    }
-  }
-  const dim3 grid(static_cast<unsigned>(tiles));
-  auto launch = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(64 * waves), 0, s, ka); };
-  if (waves == 16) {
-    if (NG == 2) launch(kv_gemm_kernel<true, 2, 16>);
-    else if (NG == 3) launch(kv_gemm_kernel<true, 3, 16>);
-    else launch(kv_gemm_kernel<true, 4, 16>);
-  } else if (f16) {
-    if (NG == 2) launch(kv_gemm_kernel<true, 2, 8>);
-    else if (NG == 3) launch(kv_gemm_kernel<true, 3, 8>);
-    else launch(kv_gemm_kernel<true, 4, 8>);
-  } else {
-    if (NG == 2) launch(kv_gemm_kernel<false, 2, 8>);
-    else if (NG == 3) launch(kv_gemm_kernel<false, 3, 8>);
-    else launch(kv_gemm_kernel<false, 4, 8>);
-  }
-  HBK_LAUNCH_CHECK("kv_gemm_kernel");
-  return HBK_OK;
-}
-
-int mlp_eval_count(const hbk_mlp_plan& p, const float* params, const void* pool, bool f16, int64_t n_pool,
-                   const int32_t* idx, int64_t rows, int64_t r0, int label, float act_thr, float drop_p,
-                   uint64_t seed, float* counts, float* prob, float* ws, hipStream_t s) {
-  if (rows <= 0) return HBK_OK;
-  const EvalSeg seg{pool, n_pool, rows, r0, seed, counts, label};
-  return mlp_eval_launch(p, params, f16, &seg, 1, idx, act_thr, drop_p, prob, ws, s);
-}
-
-int mlp_eval_count_multi(const hbk_mlp_plan& p, const float* params, bool f16, const EvalSeg* seg, int nseg,
-                         float act_thr, float drop_p, float* ws, hipStream_t s) {
-  EvalSeg live[kKvMaxSeg];
-  int n = 0;
-  for (int i = 0; i < nseg; ++i)
-    if (seg[i].rows > 0) live[n++] = seg[i];
-  if (n == 0) return HBK_OK;
-  return mlp_eval_launch(p, params, f16, live, n, nullptr, act_thr, drop_p, nullptr, ws, s);
-}
-
-int mlp_eval_finish(const float* cv, const float* ct, const double* sizes, float target, float ratio, float* sched,
-                    int64_t sched_len, int64_t next_step, float* out, hipStream_t s) {
-  EvalFinish f;
-  f.cv = cv;
-  f.ct = ct;
-  f.n_neg_v = static_cast<float>(sizes[0]);
-  f.n_pos_v = static_cast<float>(sizes[1]);
-  f.n_neg_t = static_cast<float>(sizes[2]);
-  f.n_pos_t = static_cast<float>(sizes[3]);
-  f.hours_v = static_cast<float>(sizes[0] * 1.44 / 3600.0);
-  f.target = target;
-  f.ratio = ratio;
-  f.sched = sched;
-  f.sched_len = sched_len;
-  f.next_step = next_step;
-  f.out = out;
-  hipLaunchKernelGGL(kv_finish_kernel, dim3(1), dim3(256), 0, s, f);
-  HBK_LAUNCH_CHECK("kv_finish_kernel");
   return HBK_OK;
 }
 

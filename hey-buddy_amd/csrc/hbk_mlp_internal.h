@@ -1,11 +1,14 @@
-// The classifier plan shared by hbk_mlp.hip (generic GEMM path, any dims) and
-// hbk_mlp_fused.hip (fused train step for the default architecture).
+// The classifier plan shared by hbk_mlp.hip (generic GEMM path, any dims) and the
+// fused path for the default architecture: hbk_mlp_fused.hip (train step) and
+// hbk_mlp_eval.hip (evaluation passes).
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <vector>
+
+#include "hbk_mlp_dims.h"
 
 namespace hbk {
 
@@ -54,8 +57,17 @@ __device__ __forceinline__ float adam_step(float mi, float vi, float step_size, 
   return step_size * mi * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(vi) * inv_bc2s + eps);
 }
 
-// True when the fused kernels of hbk_mlp_fused.hip cover this plan.
+// True when the fused kernels (train step: hbk_mlp_fused.hip; evaluation passes:
+// hbk_mlp_eval.hip) cover this plan.
 bool mlp_fused_supported(const hbk_mlp_plan& p);
+// The weight cache both read (f16 hi / lo planes of W_o_k, k < NG - 1, and W_hg_k, k >= 1, as
+// stored and transposed; hbk_mlp_dev.h: WSplit): its planes' offsets in halves from the cache
+// base, and its fill from the parameters (k0_wsplit_kernel, in hbk_mlp_fused.hip)
+struct WCacheOffsets {
+  int64_t c_o[kMaxG], c_oT[kMaxG], c_hg[kMaxG], c_hgT[kMaxG];
+};
+WCacheOffsets mlp_wcache_offsets(const hbk_mlp_plan& p);
+int mlp_wcache_fill(const hbk_mlp_plan& p, const float* params, float* cache, hipStream_t s);
 int64_t mlp_fused_ws_floats(const hbk_mlp_plan& p, int64_t B);
 // 1 (k1a / k1b / k3) or 2 (k1s / k1c / k3s): the train step mlp_fused_run takes for B rows on s
 int mlp_fused_step_variant(int64_t B, hipStream_t s);

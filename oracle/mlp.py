@@ -286,8 +286,9 @@ def flat_bucket(params, x, y, neg_weight=1.0, threshold=1e-4, act_thr=0.5):
 
 # ------------------------------------------------------------ evaluation ----
 def dropout_keep(seed: int, row_ids, d: int = 1536, p: float = 0.1) -> np.ndarray:
-    """The counter-based input-dropout mask of the HIP kernels (k1a_tile /
-    kv_gemm_kernel, hbk_mlp_fused.hip: drop_hash): element c of row r is dropped
+    """The counter-based input-dropout mask of the HIP kernels (k1a_tile in
+    hbk_mlp_fused.hip, kv_gemm_kernel in hbk_mlp_eval.hip; drop_hash in
+    hbk_mlp_dev.h): element c of row r is dropped
     iff a 16-bit uniform from hash(seed, r * d / 2 + c / 2) (low half for even c,
     high half for odd c) is below round(p * 65536). [n, d] bool (True = kept).
     The reference draws torch's Philox mask instead; only the rate matches."""

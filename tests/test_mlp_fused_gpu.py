@@ -1,8 +1,8 @@
-"""The fused classifier train step (hbk_mlp_step_*, hbk_mlp_fused.hip) on the
-GPU: against the reference's own outputs (tests/golden/classifier.npz), against
-the generic GEMM path at the stage batch sizes 1100 / 550 / 273 (and ragged
-ones), and the index-gathered multi-step graph (train_indexed) against eager
-steps.
+"""The fused classifier train step (hbk_mlp_step_*: hbk_mlp_fused.hip, planned
+by hbk_mlp_plan.h) on the GPU: against the reference's own outputs
+(tests/golden/classifier.npz), against the generic GEMM path at the stage batch
+sizes 1100 / 550 / 273 (and ragged ones), and the index-gathered multi-step
+graph (train_indexed) against eager steps.
 
 Tolerances: gradients 1e-4 of each tensor's max |g| (f32, summation order
 and float-atomic order differ from torch's); loss 1e-5 relative.
