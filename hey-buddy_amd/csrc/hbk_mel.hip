@@ -104,12 +104,9 @@ __device__ __forceinline__ void fft4(C& a0, C& a1, C& a2, C& a3) {
   a3 = csub(t1, t3);
 }
 
-// In-register 16-point forward DFT: v[k] <- sum_n v[n] W16^(nk), natural order.
+// fft16 after its first radix-4 stage (over m1 for each m2: v[4 l1 + m2] = A[m2][l1])
 template <class C>
-__device__ __forceinline__ void fft16(C (&v)[16]) {
-  // n = 4 m1 + m2: radix-4 over m1 for each m2 -> v[4 l1 + m2] = A[m2][l1]
-#pragma unroll
-  for (int m2 = 0; m2 < 4; ++m2) fft4(v[m2], v[4 + m2], v[8 + m2], v[12 + m2]);
+__device__ __forceinline__ void fft16_tail(C (&v)[16]) {
 #pragma unroll
   for (int l1 = 1; l1 < 4; ++l1)
 #pragma unroll
@@ -123,6 +120,59 @@ __device__ __forceinline__ void fft16(C (&v)[16]) {
 #pragma unroll
   for (int k = 0; k < 16; ++k) v[k] = t[k];
 }
+// In-register 16-point forward DFT: v[k] <- sum_n v[n] W16^(nk), natural order.
+template <class C>
+__device__ __forceinline__ void fft16(C (&v)[16]) {
+  // n = 4 m1 + m2: radix-4 over m1 for each m2 -> v[4 l1 + m2] = A[m2][l1]
+#pragma unroll
+  for (int m2 = 0; m2 < 4; ++m2) fft4(v[m2], v[4 + m2], v[8 + m2], v[12 + m2]);
+  fft16_tail(v);
+}
+
+// The FFT16 over n1 of a windowed frame, v[k] <- sum_n (x[n] w[n]) W16^(nk) with x[n] w[n]
+// elementwise (re and im are two real samples), for the kernels whose persistent loop is
+// written as two copies of its body (v2, MFMA). The window products are fused into the first
+// radix-4 stage here, by hand, and nothing in this block is left to -ffp-contract=fast: the
+// compiler contracted x w + x' w' differently in the two copies (EDGE0 = true: 152 / 142 FMAs),
+// so the last bit of a frame depended on the round of the loop it fell in, i.e. on the grid
+// size (the stream's CU mask). EDGE0: rows 0 and 15 are zero and never read.
+#pragma clang fp contract(off)
+__device__ __forceinline__ sc emul(sc a, sc b) { return {a.x * b.x, a.y * b.y}; }
+__device__ __forceinline__ cf emul(cf a, cf b) { return a * b; }
+__device__ __forceinline__ sc efma(sc a, sc b, sc c) { return {fmaf(a.x, b.x, c.x), fmaf(a.y, b.y, c.y)}; }
+__device__ __forceinline__ cf efma(cf a, cf b, cf c) { return __builtin_elementwise_fma(a, b, c); }
+__device__ __forceinline__ sc eneg(sc a) { return {-a.x, -a.y}; }
+__device__ __forceinline__ cf eneg(cf a) { return -a; }
+template <bool EDGE0, class C>
+__device__ __forceinline__ void fft16_windowed_stage1(const C (&x)[16], const C (&w)[16], C (&v)[16]) {
+#pragma unroll
+  for (int m2 = 0; m2 < 4; ++m2) {
+    // a0 .. a3 = rows m2, 4 + m2, 8 + m2, 12 + m2; t0 = a0 + a2, t1 = a0 - a2, t2 = a1 + a3, d = a1 - a3
+    const C p2 = emul(x[8 + m2], w[8 + m2]);
+    C t0, t1, t2, d;
+    if (EDGE0 && m2 == 0) {
+      t0 = p2;
+      t1 = eneg(p2);
+    } else {
+      t0 = efma(x[m2], w[m2], p2);
+      t1 = efma(x[m2], w[m2], eneg(p2));
+    }
+    if (EDGE0 && m2 == 3) {
+      t2 = emul(x[4 + m2], w[4 + m2]);
+      d = t2;
+    } else {
+      const C p3 = emul(x[12 + m2], w[12 + m2]);
+      t2 = efma(x[4 + m2], w[4 + m2], p3);
+      d = efma(x[4 + m2], w[4 + m2], eneg(p3));
+    }
+    const C t3 = cmul_mi(d);
+    v[m2] = cadd(t0, t2);
+    v[8 + m2] = csub(t0, t2);
+    v[4 + m2] = cadd(t1, t3);
+    v[12 + m2] = csub(t1, t3);
+  }
+}
+#pragma clang fp contract(fast)
 
 __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -380,16 +430,15 @@ mel_frames_v2_kernel(Mel2Args a) {
   auto process = [&](uint32_t grp, const C (&cur)[16], C (&nxt)[16]) {
     // window and twiddles come from the LDS table in two batches of reads
     // (one wait each) instead of VGPR-resident window + per-use twiddle reads
-    C v[16];
+    C v[16], w[16];
 #pragma unroll
-    for (int n1 = n1lo; n1 < n1hi; ++n1) v[n1] = cpx<C>(cj[16 * (kCWin + n1)]);
+    for (int n1 = n1lo; n1 < n1hi; ++n1) w[n1] = cpx<C>(cj[16 * (kCWin + n1)]);
     C tw[16];
 #pragma unroll
     for (int k1 = 1; k1 < 16; ++k1) tw[k1] = cpx<C>(cj[16 * (kCTw + k1)]);
-#pragma unroll
-    for (int n1 = 0; n1 < 16; ++n1) v[n1] = (n1 < n1lo || n1 >= n1hi) ? C{0.f, 0.f} : cur[n1] * v[n1];
+    fft16_windowed_stage1<EDGE0>(cur, w, v);
     load(frame_src(grp + gridDim.x), nxt);  // prefetch (clamped past the end)
-    fft16(v);
+    fft16_tail(v);
 #pragma unroll
     for (int k1 = 1; k1 < 16; ++k1) v[k1] = cmul(v[k1], tw[k1]);
 #pragma unroll
@@ -597,16 +646,15 @@ mel_frames_mfma_kernel(Mel3Args a) {
   };
 
   auto process = [&](uint32_t grp, const C (&cur)[16], C (&nxt)[16]) {
-    C v[16];
+    C v[16], w[16];
 #pragma unroll
-    for (int n1 = n1lo; n1 < n1hi; ++n1) v[n1] = cpx<C>(cj[16 * (kCWin3 + n1)]);
+    for (int n1 = n1lo; n1 < n1hi; ++n1) w[n1] = cpx<C>(cj[16 * (kCWin3 + n1)]);
     C tw[16];
 #pragma unroll
     for (int k1 = 1; k1 < 16; ++k1) tw[k1] = cpx<C>(cj[16 * (kCTw + k1)]);
-#pragma unroll
-    for (int n1 = 0; n1 < 16; ++n1) v[n1] = (n1 < n1lo || n1 >= n1hi) ? C{0.f, 0.f} : cur[n1] * v[n1];
+    fft16_windowed_stage1<EDGE0>(cur, w, v);
     load(frame_src(grp + gridDim.x), nxt);  // prefetch (clamped past the end)
-    fft16(v);
+    fft16_tail(v);
 #pragma unroll
     for (int k1 = 1; k1 < 16; ++k1) v[k1] = cmul(v[k1], tw[k1]);
 #pragma unroll
@@ -995,6 +1043,15 @@ struct hbk_mel_plan {
   float4* d_t4 = nullptr;
 };
 
+// The kernel hbk_mel_frames launches for a plan (hbk_mel_plan_info's numbering):
+// 1 = v1, 2 = v2, 3 = MFMA, 4 / 8 = SoA with 4 / 8 waves per block.
+static int mel_route(const hbk_mel_plan* plan) {
+  if (!plan->v2) return 1;
+  if (plan->variant == 1) return 3;
+  if (plan->v4) return plan->v4 == 8 ? 8 : 4;
+  return 2;
+}
+
 extern "C" {
 
 int hbk_mel_plan_create(const float* window, const float* fbank, int n_fft, int hop, int n_mels,
@@ -1196,6 +1253,19 @@ int hbk_mel_set_variant(hbk_mel_plan* plan, int32_t variant) {
   return HBK_OK;
 }
 
+int hbk_mel_plan_info(const hbk_mel_plan* plan, int32_t info[8]) {
+  using namespace hbk;
+  if (!plan || !info) return arg_error("plan/info is NULL");
+  info[0] = mel_route(plan);
+  info[1] = plan->edge0;
+  info[2] = plan->taps;
+  info[3] = plan->nk2;
+  info[4] = plan->need256;
+  info[5] = plan->n_mels;
+  info[6] = info[7] = 0;
+  return HBK_OK;
+}
+
 int hbk_mel_frames(const hbk_mel_plan* plan, const float* pcm, int64_t n_clips, int64_t clip_stride,
                    int64_t n_frames, float* out, void* stream) {
   using namespace hbk;
@@ -1209,7 +1279,8 @@ int hbk_mel_frames(const hbk_mel_plan* plan, const float* pcm, int64_t n_clips, 
   if (plan->hop * (n_frames - 1) + plan->n_fft > clip_stride) return arg_error("frames exceed clip_stride");
   const int64_t total = n_clips * n_frames;
   if (total >= (int64_t(1) << 31)) return arg_error("more than 2^31 frames in one call");
-  if (plan->v2 && plan->variant == 1) {
+  const int route = mel_route(plan);
+  if (route == 3) {
     const int64_t groups3 = (total + kFramesPerBlock3 - 1) / kFramesPerBlock3;
     Mel3Args a;
     a.pcm = pcm;
@@ -1235,8 +1306,8 @@ int hbk_mel_frames(const hbk_mel_plan* plan, const float* pcm, int64_t n_clips, 
     HBK_LAUNCH_CHECK("mel_frames_mfma_kernel");
     return HBK_OK;
   }
-  if (plan->v2 && plan->v4) {
-    const int W = plan->v4 == 8 ? 8 : 4;  // waves per block (hbk_mel_plan::v4)
+  if (route == 4 || route == 8) {
+    const int W = route;  // waves per block (hbk_mel_plan::v4)
     const int64_t fpb = kFramesPerWave4 * W;
     const int64_t groups4 = (total + fpb - 1) / fpb;
     Mel4Args a;
@@ -1267,7 +1338,7 @@ int hbk_mel_frames(const hbk_mel_plan* plan, const float* pcm, int64_t n_clips, 
     HBK_LAUNCH_CHECK("mel_frames_soa_kernel");
     return HBK_OK;
   }
-  if (plan->v2) {
+  if (route == 2) {
     const int64_t groups2 = (total + kFramesPerBlock2 - 1) / kFramesPerBlock2;
     Mel2Args a;
     a.pcm = pcm;

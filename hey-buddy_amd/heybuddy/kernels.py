@@ -76,6 +76,14 @@ class MelPlan:
         check(lib().hbk_mel_set_variant(self._handle, int(variant)), "hbk_mel_set_variant")
         return self
 
+    def info(self) -> dict:
+        """What hbk_mel_frames launches for this plan now (hbk_mel_plan_info):
+        kernel 1 = v1, 2 = v2, 3 = MFMA, 4 / 8 = SoA with 4 / 8 waves; edge0,
+        taps, nk2, need256, n_mels."""
+        buf = (ctypes.c_int32 * 8)()
+        check(lib().hbk_mel_plan_info(self._handle, buf), "hbk_mel_plan_info")
+        return dict(zip(("kernel", "edge0", "taps", "nk2", "need256", "n_mels"), (int(v) for v in buf)))
+
     def __call__(self, pcm: torch.Tensor, n_frames: int | None = None) -> torch.Tensor:
         return mel_frames(pcm, self, n_frames)
 

@@ -74,7 +74,11 @@ typedef struct hbk_mel_plan hbk_mel_plan;
  * log_floor: clamp before 10*log10 (1e-10, AmplitudeToDB amin);
  * out_div, out_add: y = 10*log10(max(mel, floor)) / out_div + out_add
  *   (10, 2: spectrogram.py:32).
- * Supported: n_fft == 512, n_mels <= 64 and even. */
+ * Supported: n_fft == 512, n_mels <= 32 and even, every filter's non-zero
+ * bins within 16 consecutive bins (else HBK_ERR_UNSUPPORTED).
+ * The environment variables HBK_MEL_V1, HBK_MEL_V4 and HBK_MEL_MFMA are read
+ * here, at plan creation, and never again: they pick the kernel the plan
+ * launches (hbk_mel_plan_info). */
 int hbk_mel_plan_create(const float* window, const float* fbank, int n_fft,
                         int hop, int n_mels, float in_scale, float log_floor,
                         float out_div, float out_add, hbk_mel_plan** plan);
@@ -84,6 +88,21 @@ int hbk_mel_plan_destroy(hbk_mel_plan* plan);
  * only; HBK_MEL_MFMA=1 in the environment selects it at plan creation).
  * Same transform and outputs (within the 1e-4 tolerance). */
 int hbk_mel_set_variant(hbk_mel_plan* plan, int32_t variant);
+/* What hbk_mel_frames will launch for the plan's current variant (host only):
+ *   info[0] kernel: 1 = v1, the general kernel (any supported filterbank);
+ *           2 = v2 (32 mels, every filter below bin 128 and inside 8 taps
+ *           (mels 0-15) / 16 taps (mels 16-31) from an even start bin;
+ *           HBK_MEL_V1 in the environment forces 1 instead);
+ *           3 = v2's transform with the MFMA filterbank (variant 1);
+ *           4 / 8 = the SoA kernel with 4 / 8 waves per block (a v2 plan
+ *           created under HBK_MEL_V4=1 / HBK_MEL_V4=8);
+ *   info[1] edge0: the kernel skips the first and last 32 samples of a frame
+ *           (the window is zero there; always 0 for kernel 1);
+ *   info[2] taps: the widest filter's run of bins (kernel 1's loop count);
+ *   info[3] nk2: 16-bin blocks of the spectrum kernel 1 computes;
+ *   info[4] need256: kernel 1 computes the Nyquist bin;
+ *   info[5] n_mels; info[6..7] = 0. */
+int hbk_mel_plan_info(const hbk_mel_plan* plan, int32_t info[8]);
 
 /* pcm: [n_clips, clip_stride] f32; frames f in [0, n_frames) of every clip
  *   (caller guarantees hop*(n_frames-1) + n_fft <= samples per clip);
