@@ -25,16 +25,13 @@
 #include <vector>
 
 #include "hbk_common.h"
+#include "hbk_embed_args.h"  // kernel-argument structs and geometry constants
+#include "hbk_embed_plan.h"  // the host planner (no device call)
 
 namespace hbk {
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
-constexpr int kMaxStages = 10;
-constexpr int kMaxWin = 32;
-constexpr int kLdsBudget = 78 * 1024;     // bytes per block: 2 blocks per CU
-constexpr int kLdsBudgetCU = 156 * 1024;  // one block per CU
 constexpr int kChunkClips = 16384;     // clips per workspace chunk (default; HBK_EMBED_CHUNK overrides)
 // clips per workspace chunk (HBK_EMBED_CHUNK: 256 .. 32,768): every chain kernel runs once per chunk (its last round of waves
 // partly filled); measured: 100 k clips in 16,384-clip chunks 24.30 ms, in 32,768-clip chunks
@@ -51,39 +48,6 @@ inline int64_t chunk_clips() {
 }
 
 typedef float f4 __attribute__((ext_vector_type(4)));
-
-struct StageDesc {
-  int kh, kw, cin, cinp, cout, coutp;
-  int K, ksteps, act;
-  float alpha;
-  int w_off, b_off;  // floats into the chain's weight blob
-};
-
-struct ChainArgs {
-  const float* in;
-  float* out;
-  const float* wblob;
-  int64_t n_img;            // images (clips or windows)
-  int64_t src_clip_stride;  // floats between source clips
-  int src_row_stride;       // floats between source rows
-  int ipc;                  // images per source clip
-  int row_off[kMaxWin];     // source row offset of image (i % ipc)
-  int C_src;
-  int in_ph, in_pw;         // input max-pool
-  int W_in;                 // chain input width after the input pool
-  int out_ph, out_pw;       // output max-pool
-  int H_out, W_out, C_out;  // chain output per image
-  int64_t out_img_stride;   // floats between output images
-  int G;                    // images per task
-  int band;                 // output rows per task
-  int n_bands;
-  int shrink;               // sum over stages of kh - 1
-  int n_stages;
-  StageDesc st[kMaxStages];
-  int wblob_floats;
-  int wstride;              // row stride of packed weights
-  int lds_x, lds_y, lds_w, lds_k;  // float offsets into dynamic LDS
-};
 
 template <int NB, int RB, bool WG>
 __device__ __forceinline__ void conv_stage(const float* __restrict__ X, float* __restrict__ Y,
@@ -268,57 +232,11 @@ __global__ void __launch_bounds__(kThreads) conv_chain_kernel(ChainArgs a) {
 // mel input, cin 1) is expanded im2col-style during staging and runs as a
 // 1x1 conv. Staging / store loops use a per-kernel 2-D thread mapping (row x
 // unit) so no integer division runs per element.
-constexpr int kXThreads = 256;
 constexpr int kXWaves = kXThreads / 64;
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef __fp16 h2 __attribute__((ext_vector_type(2)));
 typedef float f16x __attribute__((ext_vector_type(16)));
-
-struct XStage {
-  int kh, kw, cin, cout;
-  int coutr;          // output channels written (cout rounded up to 8; the pad is exactly 0)
-  int cs_in, cs_out;  // fp16 elements per position of the input / output tensor
-  int ksteps;         // K steps of 16 (two 8-channel groups)
-  int nblk;           // 32-wide output-channel blocks
-  int act;
-  float alpha;
-  int w_off;          // fp16 offset of the hi plane [nblk * 32][wrow]
-  int w_lo;           // fp16 distance hi -> lo plane
-  int wrow;
-  int b_off;          // float offset into the bias blob
-  int kt_off;         // int offset of the stage's group-offset table
-};
-
-struct XArgs {
-  const float* in;
-  float* out;
-  const _Float16* wblob;   // global weights (WG mode reads them here)
-  const float* bblob;      // biases [per stage nblk * 32]
-  const int* ktab;         // group offsets, all stages
-  const int* i2c_off;      // im2col: raw-row offset of tap k = (dh kw + dw) C + ci
-  int i2c_n;
-  int64_t n_img;
-  int64_t src_clip_stride;
-  int src_row_stride;
-  int ipc;
-  int row_off[kMaxWin];
-  int C_src, cs0;          // source channels; fp16 stride of the staged tensor
-  int im2col;              // stage 0 input is the im2col expansion (K0 = kh kw cin)
-  int in_ph, in_pw, W_in;
-  int out_ph, out_pw, H_out, W_out, C_out;
-  int64_t out_img_stride;
-  int vec_out;             // C_out % 4 == 0 and 16-B aligned output: float4 stores
-  int raw_vec;             // im2col staging reads float4 (in_pw == 1, aligned rows)
-  int G, band, n_bands, shrink, n_stages;
-  XStage st[kMaxStages];
-  int w_halfs;             // resident weights (0: WG mode)
-  int b_floats, kt_n;
-  int lds_x, lds_y, lds_w, lds_b, lds_k;  // byte offsets into dynamic LDS
-  int dbg_slot;            // phase-timing slot (chain index mod 4; profiling build only)
-  int dbg_skip;            // profiling build only: bit 0 stages, 1 im2col, 2 store, 3 staging
-  int* range_flag;         // set to 1 when an f16-split value reaches kF16Max
-};
 
 #if defined(HBK_PHASE_TIMING) || defined(HBK_ABLATE)
 #define HBK_SKIP(bit) (a.dbg_skip & (1 << (bit)))
@@ -391,10 +309,7 @@ __device__ __forceinline__ int div_small(int n, int d, float inv) {
 // hi = v rounded toward zero to fp16 (11 significant bits in fp16's normal
 // range), lo = (v - hi) rounded to fp16 by v_fma_mix{lo,hi}_f16 (v - hi is
 // exact in f32); two values, packed: 3 VALU instructions per pair
-// The f16 planes hold |v| < 65504 (kF16Max): amax keeps the largest |v| a
-// thread split (one v_max3 per pair; fmaxf drops NaN, which is not a range
-// fault) and the kernel raises its plan's range flag when it reaches kF16Max.
-constexpr float kF16Max = 65504.f;
+// (kF16Max and the range flag: hbk_embed_args.h)
 // (one v_max3 through asm: fmaxf / fabsf put canonicalising v_max ops in front)
 __device__ __forceinline__ void track(float& amax, float a, float b) {
   asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(amax) : "v"(a), "v"(b));
@@ -944,39 +859,7 @@ conv_chain_x3_kernel(XArgs a) {
 //     plus v_fma_mix{lo,hi}_f16 (lo = x - hi rounded to fp16);
 //   * one task = one image x BAND pooled rows (4 waves, 32-position tiles
 //     round-robin over the waves), 2 blocks / CU.
-constexpr int kP0Waves = 4;
-constexpr int kP0Threads = 64 * kP0Waves;
-
-struct P0Args {
-  const float* in;          // [img][rows][WI] f32, row stride WI
-  float* out;               // [img][H_out][W2 / 2][C] f32
-  const _Float16* w;        // stage s: hi [32][16 ks_s], lo [32][16 ks_s]
-  const float* bias;        // [3][32] (rows >= C are 0)
-  int64_t n_img;
-  int64_t src_img_stride;   // floats
-  int H_in;                 // valid input rows per image
-  int H_out;                // pooled output rows per image
-  int n_bands;
-  float alpha;              // LeakyReLU slope of all three convs (LEAKY kernels)
-  int* range_flag;          // set to 1 when an f16-split value reaches kF16Max
-};
-
-template <int WI, int C, int BAND>
-struct P0Geo {
-  static constexpr int W0 = WI - 2, W1 = W0 - 2, W2 = W1;
-  static constexpr int R2 = 2 * BAND, R1 = R2 + 2, R0 = R1, RI = R0 + 2;
-  static constexpr int CS = ((C / 8) % 2 == 0) ? C + 8 : C;  // odd number of 16-B groups per position
-  static constexpr int M0 = R0 * W0, M1 = R1 * W1, M2 = R2 * W2;
-  static constexpr int T0 = (M0 + 31) / 32, T1 = (M1 + 31) / 32, T2 = (M2 + 31) / 32;
-  static constexpr int KS = (3 * C + 15) / 16;  // K steps of stages 1 and 2
-  static constexpr int RAW = RI * WI * 4;
-  static constexpr int S0B = M0 * CS * 4, S1B = M1 * CS * 4, S2B = M2 * C * 4;
-  static constexpr int XB = ((RAW > S1B ? RAW : S1B) + 15) & ~15;  // raw input, then stage-1 output
-  static constexpr int YB = ((S0B > S2B ? S0B : S2B) + 15) & ~15;  // stage-0 output, then stage-2 f32
-  static constexpr int LDS = XB + YB;
-  static constexpr int WOFF1 = 2 * 32 * 16, WOFF2 = WOFF1 + 2 * 32 * 16 * KS;  // fp16 offsets
-  static constexpr int WHALFS = WOFF2 + 2 * 32 * 16 * KS;
-};
+// (P0Args, P0Geo: hbk_embed_args.h)
 
 // hi = v rounded toward zero to fp16, lo = (v - hi) rounded to fp16; two values, packed
 __device__ __forceinline__ void split2_mix(float a, float b, uint32_t& hi, uint32_t& lo, float& amax) {
@@ -1238,39 +1121,7 @@ p0_chain_kernel(P0Args a) {
 // split-f16 numerics and tile / epilogue scheme as p0_chain_kernel; the
 // stage weights do not all fit in VGPRs, so each stage's A fragments are
 // loaded (from L2) one stage ahead, while the previous stage runs.
-constexpr int kP1C = 32;
-
-struct P1Args {
-  const float* in;          // [img][H_in][WI][CI] f32
-  float* out;               // [img][H_out][W4 / 2][32] f32
-  const _Float16* w;        // stage s at woff[s]: hi [32][16 ks_s], lo [32][16 ks_s]
-  const float* bias;        // [4][32]
-  int64_t n_img;
-  int64_t src_img_stride;   // floats
-  int H_in, H_out, n_bands;
-  float alpha;
-  int* range_flag;          // set to 1 when an f16-split value reaches kF16Max
-};
-
-template <int WI, int CI, int BAND>
-struct P1Geo {
-  static constexpr int C = kP1C;
-  static constexpr int W0 = WI, W1 = WI - 2, W2 = W1, W3 = W1 - 2, W4 = W3;
-  static constexpr int R4 = 2 * BAND, R3 = R4 + 2, R2 = R3, R1 = R2 + 2, R0 = R1;
-  static constexpr int CSI = ((CI / 8) % 2 == 0) ? CI + 8 : CI;
-  static constexpr int CS = ((C / 8) % 2 == 0) ? C + 8 : C;
-  static constexpr int M1 = R1 * W1, M2 = R2 * W2, M3 = R3 * W3, M4 = R4 * W4;
-  static constexpr int KS1 = (3 * CI + 15) / 16, KS = (3 * C + 15) / 16;
-  static constexpr int KSMAX = KS1 > KS ? KS1 : KS;
-  static constexpr int INB = R0 * W0 * CSI * 4, S1B = M1 * CS * 4, S2B = M2 * CS * 4, S3B = M3 * CS * 4,
-                       S4B = M4 * C * 4;
-  static constexpr int mx(int a, int b) { return a > b ? a : b; }
-  static constexpr int XB = (mx(mx(INB, S2B), S4B) + 15) & ~15;  // input, stage-2 out, stage-4 out (f32)
-  static constexpr int YB = (mx(S1B, S3B) + 15) & ~15;            // stage-1 out, stage-3 out
-  static constexpr int LDS = XB + YB;
-  static constexpr int WOFF1 = 0, WOFF2 = WOFF1 + 2 * 32 * 16 * KS1, WOFF3 = WOFF2 + 2 * 32 * 16 * KS,
-                       WOFF4 = WOFF3 + 2 * 32 * 16 * KS, WHALFS = WOFF4 + 2 * 32 * 16 * KS;
-};
+// (P1Args, P1Geo: hbk_embed_args.h)
 
 template <int KS>
 __device__ __forceinline__ P0W<KS> p1_load_w(const _Float16* w, const float* bias, int r32, int khalf) {
@@ -1448,17 +1299,7 @@ p1_chain_kernel(P1Args a) {
 // Raw rows: one dword per lane per row, loaded 8-11 rows ahead; the three
 // column taps come from two DPP wave shifts. Biases ride in a padding slot
 // of K whose B value is 1 (hi 1, lo 0), so every accumulator starts at 0.
-constexpr int kP0sWaves = 4;
-constexpr int kP0sThreads = 64 * kP0sWaves;
-constexpr int kP0sCS = 24;                         // fp16 per position (3 odd 16-B groups)
-constexpr int kP0sS0Plane = 34 * kP0sCS;           // positions 0..33 (x + tap <= 33)
-constexpr int kP0sS1Plane = 32 * kP0sCS;
-constexpr int kP0sOnes = 4 * kP0sS0Plane + 8 * kP0sS1Plane;  // fp16 offset of the ones / zeros slots
-constexpr int kP0sWaveHalfs = kP0sOnes + 16;
-constexpr int kP0sLds = kP0sWaves * kP0sWaveHalfs * 2;
-constexpr int kP0sKS = 5;                          // K steps of stages 1 and 2 (72 + bias slot)
-constexpr int kP0sRows = 136, kP0sHout = 66, kP0sWout = 14, kP0sC = 24;
-
+// (the kP0s* geometry: hbk_embed_args.h)
 struct P0sW {
   h8 h[kP0sKS], l[kP0sKS];
 };
@@ -1716,19 +1557,7 @@ p0s_chain_kernel(P0Args a) {
 //   b: g = dy * 4 + c    -> A row (r + dy), position x, channels 8 c
 //   c: g = dx * 4 + c    -> B position x + dx, channels 8 c
 //   d: g = dy * 4 + c    -> C row (r + dy), position x, channels 8 c
-constexpr int kP1sThreads = 128;
-constexpr int kP1sCSI = 24, kP1sCS = 40;          // fp16 per position: input (24 ch), stage outputs (32 ch)
-constexpr int kP1sInPlane = 18 * kP1sCSI;         // 18 positions (14 valid; x + tap <= 17)
-constexpr int kP1sInSlot = 2 * kP1sInPlane + 32;  // hi, lo, then ones (hi 8, lo 8) and zeros (hi 8, lo 8)
-constexpr int kP1sPlane = 16 * kP1sCS;            // A / C rows
-constexpr int kP1sBPlane = 18 * kP1sCS;           // B rows (c reads x + dx <= 17)
-constexpr int kP1sIn = 0, kP1sA = kP1sIn + 2 * kP1sInSlot, kP1sB = kP1sA + 4 * 2 * kP1sPlane,
-              kP1sCr = kP1sB + 2 * 2 * kP1sBPlane;
-constexpr int kP1sHalfs = kP1sCr + 4 * 2 * kP1sPlane;
-constexpr int kP1sLds = kP1sHalfs * 2;
-constexpr int kP1sHin = 66, kP1sHout = 31, kP1sWi = 14, kP1sWo = 5, kP1sCo = 32;
-constexpr int kP1sStageHalfs = 2 * 32 * 96;       // weights per stage: hi [32][96], lo [32][96]
-
+// (the kP1s* geometry: hbk_embed_args.h)
 struct P1sW {
   h8 h[2][3], l[2][3];  // [output block][K step]
 };
@@ -1971,28 +1800,7 @@ p1s_chain_kernel(P1Args a) {
 // (g = 4 ks + kq): a: g = dx * 4 + c (32 input channels); b, c, d: g = tap * 6
 // + c (48 channels), g = 18 the bias slot (B = 1), g = 19 zeros; stage a
 // starts its accumulators at the bias.
-constexpr int kP2sThreads = 512, kP2sClips = 16;
-constexpr int kP2sHin = 31, kP2sWi = 5, kP2sCi = 32, kP2sCo = 48, kP2sHout = 27;
-constexpr int kP2sCSI = 40, kP2sCS = 56;                      // fp16 per position (odd 16-B groups)
-constexpr int kP2sInPlane = kP2sClips * kP2sWi * kP2sCSI;     // one input row of 16 clips
-constexpr int kP2sAPlane = kP2sClips * 3 * kP2sCS;            // stage a / b output rows (3 columns)
-constexpr int kP2sCPlane = kP2sClips * kP2sCS;                // stage c output rows (1 column)
-constexpr int kP2sIn = 0, kP2sA = kP2sIn + 2 * 2 * kP2sInPlane, kP2sB = kP2sA + 4 * 2 * kP2sAPlane,
-              kP2sC = kP2sB + 2 * 2 * kP2sAPlane, kP2sOnes = kP2sC + 4 * 2 * kP2sCPlane;
-constexpr int kP2sHalfs = kP2sOnes + 32;
-constexpr int kP2sLds = kP2sHalfs * 2;
-constexpr int kP2sKa = 96, kP2sK = 160;                       // packed K of stage a / stages b, c, d
-constexpr int kP2sTicks = 36;                                 // rows 0 .. 30 through a 7-tick pipeline
-
-struct P2sArgs {
-  const float* in;        // [img][31][5][32] f32
-  float* out;             // [img][27][48] f32
-  const _Float16* w;      // a: hi / lo [48][96]; b, c, d: hi / lo [48][160]
-  const float* bias_a;    // [48]
-  int64_t n_img, src_img_stride;
-  float alpha;
-  int* range_flag;
-};
+// (the kP2s* geometry and P2sArgs: hbk_embed_args.h)
 
 // the wave's weights: [output block][K step] hi / lo
 template <int KS>
@@ -2247,40 +2055,7 @@ p2s_chain_kernel(P2sArgs a) {
 // five 96-channel stages for mb = wave - 4. Tick y (one barrier after it):
 // pooled row y is staged (waves 0-2, loaded a tick ahead), stage s computes its
 // row y - kT3Delay[s] (each stage reads only rows written in earlier ticks).
-constexpr int kT3Waves = 10, kT3Threads = 64 * kT3Waves, kT3Pos = 16;
-constexpr int kT3Hin = 27, kT3C0 = 48, kT3Hp = 13, kT3C1 = 64, kT3C2 = 96, kT3Hout = 8;
-constexpr int kT3Ticks = 22;
-constexpr int kT3CS0 = 56, kT3CS1 = 72, kT3CS2 = 104;  // f16 per position (odd 16-B groups)
-// ring slots (rows) and LDS offsets (f16): P (pooled, 4), A1 (2), A2 (4), A3 (2), A4 (4), A5..A8 (2 each)
-constexpr int kT3PlP = kT3Pos * kT3CS0, kT3Pl1 = kT3Pos * kT3CS1, kT3Pl2 = kT3Pos * kT3CS2;
-constexpr int kT3P = 0, kT3A1 = kT3P + 4 * 2 * kT3PlP, kT3A2 = kT3A1 + 2 * 2 * kT3Pl1,
-              kT3A3 = kT3A2 + 4 * 2 * kT3Pl1, kT3A4 = kT3A3 + 2 * 2 * kT3Pl1, kT3A5 = kT3A4 + 4 * 2 * kT3Pl1;
-constexpr int kT3Zero = kT3A5 + 4 * 2 * 2 * kT3Pl2;  // 16 zero halfs (stage 1's K padding)
-constexpr int kT3Halfs = kT3Zero + 16;
-constexpr int kT3BiasOff = kT3Halfs * 2;            // bytes: biases [4][64] then [5][96] f32
-constexpr int kT3Lds = kT3BiasOff + (4 * kT3C1 + 5 * kT3C2) * 4;
-// weights (f16, hi plane then lo plane per stage, [cout][K], K = tap * cin + ci)
-constexpr int kT3K[9] = {160, 64, 192, 64, 128, 96, 96, 96, 96};  // stage 1: 144 + 16 zero
-constexpr int kT3W[9] = {0,
-                         2 * 64 * 160,
-                         2 * 64 * (160 + 64),
-                         2 * 64 * (160 + 64 + 192),
-                         2 * 64 * (160 + 64 + 192 + 64),
-                         2 * 64 * 480 + 2 * 96 * 128,
-                         2 * 64 * 480 + 2 * 96 * (128 + 96),
-                         2 * 64 * 480 + 2 * 96 * (128 + 192),
-                         2 * 64 * 480 + 2 * 96 * (128 + 288)};
-constexpr int kT3WHalfs = 2 * 64 * 480 + 2 * 96 * 512;
-
-struct T3sArgs {
-  const float* in;      // [clip][27][48] f32 (p2s output)
-  float* out;           // [image][8][96] f32, image = 2 clip + phase
-  const _Float16* w;    // kT3WHalfs
-  const float* bias;    // [4][64] + [5][96]
-  int64_t n_img, src_clip_stride, out_img_stride;
-  float alpha;
-  int* range_flag;
-};
+// (the kT3* geometry and T3sArgs: hbk_embed_args.h)
 
 // one output block (16 channels) of one row: KS K-steps of 32, B from the
 // ring rows `rows` (tap t -> rows[t]), channel group 8 cg of tap g / (CIN / 8)
@@ -2467,1085 +2242,38 @@ t3s_chain_kernel(T3sArgs a) {
 
 // ------------------------------------------------------------------ host ----
 
-struct OpInfo {
-  int kind, kh, kw, cin, cout, act;
-  float alpha;
-  std::vector<float> w, b;  // HWIO, [cout]
-};
+// Planning is hbk_embed_plan.h (pure host); here a plan is realised on the
+// device and launched.
+static_assert(kPlanOk == HBK_OK && kPlanErrArg == HBK_ERR_ARG && kPlanErrUnsupported == HBK_ERR_UNSUPPORTED &&
+                  kOpConv == HBK_OP_CONV && kOpMaxPool == HBK_OP_MAXPOOL,
+              "hbk_embed_plan.h mirrors include/hbk.h");
 
-struct Dims {
-  int h, w, c;
+// One Launch of the host plan on the device: its kernel, its blob and its
+// arguments with the blob's pointers in place.
+struct Slot {
+  const Launch* plan = nullptr;
+  const void* fn = nullptr;  // null: nothing planned, or a pattern kernel the device refused
+  void* d_blob = nullptr;
+  int blocks_per_cu = 0;
+  KernelArgs args;
 };
-
-using KernelFn = void (*)(ChainArgs);
 
 struct ChainPlan {
-  ChainArgs args{};
-  bool split = false;        // split-f16 kernel (XArgs x) instead of the exact one
-  XArgs x{};
-  int nb = 1;
-  bool wg = false;
-  KernelFn fn = nullptr;
-  void (*xfn)(XArgs) = nullptr;
-  size_t lds_bytes = 0;
-  float* d_blob = nullptr;
-  int src_buf = -1;          // -1: the call's input, else workspace buffer index
-  int dst_buf = -1;          // -1: the call's output
-  int64_t out_floats = 0;    // per source clip (clip path) or per window
-  double macs_per_img = 0;   // algorithmic MACs per image of this chain
-  // pattern kernel (p0_chain_kernel) for this chain, if it matches; the split
-  // plan above stays as the fallback for unaligned buffers
-  void (*p0fn)(P0Args) = nullptr;
-  P0Args p0{};
-  bool p0s = false;  // p0fn is the streaming p0s_chain_kernel (one wave per image)
-  bool p1s = false;  // p1fn is the streaming p1s_chain_kernel (one wave per image)
-  void (*p2fn)(P2sArgs) = nullptr;  // p2s pattern (SE20 chain 2; shares d_p0 / p0_lds / p0_blocks_per_cu)
-  P2sArgs p2{};
-  void (*p1fn)(P1Args) = nullptr;  // p1 pattern (shares d_p0 / p0_lds / p0_blocks_per_cu)
-  P1Args p1{};
-  void (*t3fn)(T3sArgs) = nullptr;  // t3s pattern (SE20's deduplicated tail; shares d_p0 / p0_lds / ...)
-  T3sArgs t3{};
-  size_t p0_lds = 0;
-  int p0_blocks_per_cu = 0;
-  void* d_p0 = nullptr;
+  Slot pattern, base;  // tried in this order at launch
 };
-
-struct Program {
-  std::vector<ChainPlan> chains;
-  int64_t buf_floats[2] = {0, 0};  // per unit (clip or window)
-  // phase-deduplicated tail: the last chain writes [n_src rows][out_dim] per clip
-  // into workspace buffer gather_buf; output row i is source row gather_src[i]
-  int gather_buf = -1, n_src = 0;
-  std::vector<int> gather_src;
-  int* d_gather = nullptr;
-};
-
-template <int NB, int RB, bool WG>
-KernelFn kernel_for() {
-  return conv_chain_kernel<NB, RB, WG>;
-}
-
-KernelFn pick_kernel(int nb, bool wg) {
-  // RB x NB accumulators of 4 VGPRs: keep RB * NB <= 12
-  switch (nb) {
-    case 1: return wg ? kernel_for<1, 4, true>() : kernel_for<1, 4, false>();
-    case 2: return wg ? kernel_for<2, 4, true>() : kernel_for<2, 4, false>();
-    case 3: return wg ? kernel_for<3, 4, true>() : kernel_for<3, 4, false>();
-    case 4: return wg ? kernel_for<4, 2, true>() : kernel_for<4, 2, false>();
-    case 5: return wg ? kernel_for<5, 2, true>() : kernel_for<5, 2, false>();
-    default: return wg ? kernel_for<6, 2, true>() : kernel_for<6, 2, false>();
-  }
-}
-
-inline int odd_pad(int c) { return (c % 2 == 0) ? c + 1 : c; }
 
 }  // namespace
 }  // namespace hbk
 
 struct hbk_embed_plan {
-  std::vector<hbk::OpInfo> ops;
-  int in_h = 0, in_w = 0, out_dim = 0;
-  std::vector<int> starts;
-  int n_prefix = 0;
-  int seq_frames = 0;
-  int split_stride = 1;
-  bool split_f16 = true;
-  double prefix_macs = 0, tail_macs = 0;
-  hbk::Program clip_prog, win_prog;
-  int* d_range = nullptr;  // range flag of the split-f16 kernels (hbk_embed_range_status)
+  hbk::EmbedHostPlan host;
+  std::vector<hbk::ChainPlan> clip, win;  // beside host.clip.chains / host.win.chains
+  int* d_gather = nullptr;                // host.clip.gather_src
+  int* d_range = nullptr;                 // range flag of the split-f16 kernels (hbk_embed_range_status)
 };
 
 namespace hbk {
 namespace {
-
-// fp16 elements per position for c channels: rounded up to 8, with an odd
-// number of 16-B groups (conflict-free ds_read_b128 over consecutive positions).
-inline int x_cs(int c) {
-  int cs = (c + 7) & ~7;
-  if ((cs / 8) % 2 == 0) cs += 8;
-  return cs;
-}
-
-using XKernelFn = void (*)(XArgs);
-
-template <int NBMAX, bool WG>
-XKernelFn xkernel_for() {
-  return conv_chain_x3_kernel<NBMAX, WG>;
-}
-
-XKernelFn pick_xkernel(int nb, bool wg) {
-  switch (nb) {
-    case 1: return wg ? xkernel_for<1, true>() : xkernel_for<1, false>();
-    case 2: return wg ? xkernel_for<2, true>() : xkernel_for<2, false>();
-    case 3: return wg ? xkernel_for<3, true>() : xkernel_for<3, false>();
-    default: return wg ? xkernel_for<4, true>() : xkernel_for<4, false>();  // > 3 blocks: groups of 3
-  }
-}
-
-// Dynamic-LDS limit of a kernel raised to what the CU holds beside its static
-// LDS (set once to the maximum, so plans sharing the kernel never lower it).
-hipError_t set_max_dynamic_lds(const void* fn) {
-  hipFuncAttributes at;
-  hipError_t e = hipFuncGetAttributes(&at, fn);
-  if (e != hipSuccess) return e;
-  return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                             int(160 * 1024 - static_cast<int>(at.sharedSizeBytes)));
-}
-
-// Split-f16 layout of one chain whose source / pooling fields are already in
-// `a`: packs the fp16 weight planes, biases and group-offset tables, and picks
-// images-per-task and band for the LDS budget.
-int layout_split(const std::vector<OpInfo>& ops, const std::vector<int>& stage_ops, Dims d,
-                 const ChainArgs& a, ChainPlan& cp, Dims& od_out) {
-  XArgs& x = cp.x;
-  // LDS per block (default 78 KB: two blocks per CU); HBK_EMBED_LDS_KB for tuning
-  // (a chain that fits fewer than kMinG whole images per task at that budget
-  // takes a whole CU instead: measured on SE20's chain 2, 2 -> 6 images,
-  // 0.96 -> 0.81 ms per 16384 clips; the tail chain, 30 images, keeps 2 / CU)
-  constexpr int kMinG = 8;
-  const char* lds_env = getenv("HBK_EMBED_LDS_KB");
-  int64_t lds_budget = kLdsBudget;
-  if (lds_env) lds_budget = std::min<int64_t>(160, std::max(16, atoi(lds_env))) * 1024;
-  x.ipc = a.ipc;
-  for (int k = 0; k < kMaxWin; ++k) x.row_off[k] = a.row_off[k];
-  x.src_clip_stride = a.src_clip_stride;
-  x.src_row_stride = a.src_row_stride;
-  x.C_src = a.C_src;
-  x.in_ph = a.in_ph;
-  x.in_pw = a.in_pw;
-  x.W_in = a.W_in;
-  x.out_ph = a.out_ph;
-  x.out_pw = a.out_pw;
-  x.n_stages = static_cast<int>(stage_ops.size());
-  x.shrink = 0;
-  x.im2col = (d.c % 8) != 0;
-
-  std::vector<_Float16> wb;  // hi/lo planes per stage
-  std::vector<float> bb;
-  std::vector<int> kt;
-  int cin = d.c, h = d.h, w = d.w, nbmax = 1;
-  double macs = 0;
-  for (int s = 0; s < x.n_stages; ++s) {
-    const OpInfo& op = ops[stage_ops[s]];
-    if (op.cin != cin) {
-      set_error("hbk: graph channel mismatch at op %d (%d != %d)", stage_ops[s], op.cin, cin);
-      return HBK_ERR_ARG;
-    }
-    XStage& S = x.st[s];
-    S.kh = op.kh;
-    S.kw = op.kw;
-    S.cin = op.cin;
-    S.cout = op.cout;
-    S.coutr = (op.cout + 7) & ~7;
-    S.act = op.act ? ((op.alpha >= 0.f && op.alpha <= 1.f) ? 1 : 2) : 0;
-    S.alpha = op.alpha;
-    const bool i2c = x.im2col && s == 0;
-    const int K0 = op.kh * op.kw * op.cin;
-    const int cin8 = (op.cin + 7) & ~7;
-    const int groups = i2c ? (K0 + 7) / 8 : op.kh * op.kw * cin8 / 8;
-    S.cs_in = i2c ? x_cs(K0) : x_cs(op.cin);
-    S.cs_out = x_cs(op.cout);
-    S.ksteps = (groups + 1) / 2;
-    S.nblk = (op.cout + 31) / 32;
-    nbmax = std::max(nbmax, S.nblk);
-    S.wrow = S.ksteps * 16 + 8;
-    const int wo_in = w;  // this stage's input width (group offsets)
-    h -= op.kh - 1;
-    w -= op.kw - 1;
-    x.shrink += op.kh - 1;
-    if (h <= 0 || w <= 0) {
-      set_error("hbk: graph collapses the image at op %d", stage_ops[s]);
-      return HBK_ERR_ARG;
-    }
-    macs += double(h) * w * op.cout * K0;
-    // weights [n][k] (k = group * 8 + j), hi then lo plane
-    const int rows = S.nblk * 32;
-    S.w_off = static_cast<int>(wb.size());
-    S.w_lo = rows * S.wrow;
-    wb.resize(wb.size() + size_t(2) * rows * S.wrow, static_cast<_Float16>(0.f));
-    for (int n = 0; n < op.cout; ++n)
-      for (int k = 0; k < S.ksteps * 16; ++k) {
-        const int g = k / 8, j = k - g * 8;
-        int src = -1;  // index into HWIO weights (k' = tap * cin + ci)
-        if (i2c) {
-          if (k < K0) src = k;
-        } else if (g < groups) {
-          const int tap = g / (cin8 / 8), ci = (g - tap * (cin8 / 8)) * 8 + j;
-          if (ci < op.cin) src = tap * op.cin + ci;
-        }
-        if (src < 0) continue;
-        const float v = op.w[size_t(src) * op.cout + n];
-        uint32_t bits;
-        memcpy(&bits, &v, 4);
-        bits &= 0xFFFFE000u;  // hi: v rounded toward zero to 11 bits, as on the device
-        float hv;
-        memcpy(&hv, &bits, 4);
-        wb[S.w_off + size_t(n) * S.wrow + k] = static_cast<_Float16>(hv);
-        wb[S.w_off + S.w_lo + size_t(n) * S.wrow + k] = static_cast<_Float16>(v - hv);
-      }
-    S.b_off = static_cast<int>(bb.size());
-    for (int n = 0; n < rows; ++n) bb.push_back(n < op.cout ? op.b[n] : 0.f);
-    // group offsets (fp16 elements into the stage's input tensor); pad groups read offset 0
-    S.kt_off = static_cast<int>(kt.size());
-    for (int g = 0; g < 2 * S.ksteps; ++g) {
-      int v = 0;
-      if (g < groups) {
-        if (i2c) {
-          v = g * 8;
-        } else {
-          const int tap = g / (cin8 / 8), cg = g - tap * (cin8 / 8);
-          const int dh = tap / op.kw, dw = tap - dh * op.kw;
-          v = (dh * wo_in + dw) * S.cs_in + cg * 8;
-        }
-      }
-      kt.push_back(v);
-    }
-    cin = op.cout;
-  }
-  x.cs0 = x.st[0].cs_in;
-  cp.nb = nbmax;
-  std::vector<int> i2c;  // im2col tap offsets into the raw rows (stage-0 input width)
-  if (x.im2col) {
-    const XStage& S = x.st[0];
-    for (int dh = 0; dh < S.kh; ++dh)
-      for (int dw = 0; dw < S.kw; ++dw)
-        for (int ci = 0; ci < S.cin; ++ci) i2c.push_back((dh * d.w + dw) * S.cin + ci);
-  }
-  i2c.push_back(0);
-  const Dims od{h / x.out_ph, w / x.out_pw, cin};
-  if (od.h <= 0 || od.w <= 0) {
-    set_error("hbk: pooling collapses the image");
-    return HBK_ERR_ARG;
-  }
-  x.H_out = od.h;
-  x.W_out = od.w;
-  x.C_out = od.c;
-  x.out_img_stride = int64_t(od.h) * od.w * od.c;
-  x.kt_n = static_cast<int>(kt.size());
-  while (wb.size() % 8) wb.push_back(static_cast<_Float16>(0.f));
-
-  // LDS: tensor t (stage t input; t = n_stages: last output) alternates X / Y
-  auto region_bytes = [&](int G, int band, int64_t& xb, int64_t& yb) {
-    const int n = x.n_stages;
-    std::vector<int> rows(n + 1), wid(n + 1);
-    rows[n] = band * x.out_ph;
-    wid[0] = d.w;
-    for (int s = 0; s < n; ++s) wid[s + 1] = wid[s] - (x.st[s].kw - 1);
-    for (int s = n - 1; s >= 0; --s) rows[s] = rows[s + 1] + x.st[s].kh - 1;
-    xb = yb = 0;
-    for (int t = 0; t <= n; ++t) {
-      int64_t bytes;
-      if (t == 0 && x.im2col)  // stage 0 input = im2col tensor at its output geometry
-        bytes = int64_t(G) * rows[1] * wid[1] * x.st[0].cs_in * 4;
-      else
-        bytes = int64_t(G) * rows[t] * wid[t] * (t == 0 ? x.st[0].cs_in : x.st[t - 1].cs_out) * 4;
-      int64_t& r = (t % 2 == 0) ? xb : yb;
-      r = std::max(r, bytes);
-    }
-    if (x.im2col) yb = std::max(yb, int64_t(G) * rows[0] * wid[0] * d.c * 4);  // raw f32 rows
-    xb = (xb + 15) & ~int64_t(15);
-    yb = (yb + 15) & ~int64_t(15);
-  };
-  const int64_t w_bytes = int64_t(wb.size()) * 2, k_bytes = (int64_t(kt.size()) * 4 + 15) & ~int64_t(15);
-  const int64_t b_bytes = int64_t(bb.size()) * 4;  // multiple of 128
-  auto lds_total = [&](int G, int band, bool resident) {
-    int64_t xb, yb;
-    region_bytes(G, band, xb, yb);
-    return xb + yb + (resident ? w_bytes : 0) + b_bytes + k_bytes;
-  };
-  // MACs computed per output row of the whole image for a band of b rows
-  // (halo rows recomputed by every band): useful / computed = efficiency.
-  auto efficiency = [&](int b) {
-    const int n = x.n_stages, nb = (od.h + b - 1) / b;
-    double useful = 0, done = 0;
-    int rows_b = b * x.out_ph, rows_full = od.h * x.out_ph;
-    for (int s = n - 1; s >= 0; --s) {
-      const XStage& S = x.st[s];
-      int wo = d.w;
-      for (int q = 0; q <= s; ++q) wo -= x.st[q].kw - 1;
-      const double per_row = double(wo) * S.cout * S.kh * S.kw * S.cin;
-      useful += per_row * rows_full;
-      done += per_row * rows_b * nb;
-      rows_b += S.kh - 1;
-      rows_full += S.kh - 1;
-    }
-    return useful / done;
-  };
-  auto best_band = [&](bool res) {
-    for (int b = od.h; b >= 1; --b)
-      if (lds_total(1, b, res) <= lds_budget) return b;
-    return 0;
-  };
-  bool resident = false;
-  int band = 0, G = 1;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    // resident weights unless they cost more than 5 % of the work in halo rows
-    // (HBK_EMBED_WEIGHTS=lds|global overrides, for tuning)
-    const int band_r = lds_total(1, 1, true) <= lds_budget ? best_band(true) : 0;
-    const int band_g = best_band(false);
-    resident = band_r > 0 && (band_g == 0 || efficiency(band_r) >= 0.95 * efficiency(band_g));
-    if (const char* wp = getenv("HBK_EMBED_WEIGHTS")) {
-      if (!strcmp(wp, "global") && band_g > 0) resident = false;
-      if (!strcmp(wp, "lds") && band_r > 0) resident = true;
-    }
-    band = resident ? band_r : band_g;
-    G = 1;
-    if (band == 0) {
-      set_error("hbk: one output row of a chain does not fit in LDS");
-      return HBK_ERR_UNSUPPORTED;
-    }
-    if (band == od.h)
-      while (G < 64 && lds_total(G + 1, band, resident) <= lds_budget) ++G;  // any G: fill the LDS budget
-    if (attempt == 0 && !lds_env && band == od.h && G < kMinG) {
-      lds_budget = kLdsBudgetCU;
-      continue;
-    }
-    break;
-  }
-  x.G = G;
-  x.band = band;
-  x.n_bands = (od.h + band - 1) / band;
-  int64_t xb, yb;
-  region_bytes(G, band, xb, yb);
-  x.lds_x = 0;
-  x.lds_y = static_cast<int>(xb);
-  x.lds_w = static_cast<int>(xb + yb);
-  x.lds_b = x.lds_w + static_cast<int>(resident ? w_bytes : 0);
-  x.lds_k = x.lds_b + static_cast<int>(b_bytes);
-  x.w_halfs = resident ? static_cast<int>(wb.size()) : 0;
-  x.b_floats = static_cast<int>(bb.size());
-  x.vec_out = od.c % 4 == 0;  // cleared at launch for an unaligned output
-  x.raw_vec = x.im2col && x.in_pw == 1 && (x.W_in * x.C_src) % 4 == 0;  // and at launch: alignment
-  cp.lds_bytes = size_t(x.lds_k + k_bytes);
-  cp.wg = !resident;
-  cp.split = true;
-  cp.xfn = pick_xkernel(nbmax, cp.wg);
-  // device blob: weights (fp16), biases (f32), group offsets (int)
-  const size_t wsz = wb.size() * 2, bsz = ((bb.size() * 4 + 15) & ~size_t(15));
-  const size_t ksz = (kt.size() * 4 + 15) & ~size_t(15), isz = i2c.size() * 4;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&cp.d_blob), wsz + bsz + ksz + isz);
-  if (e != hipSuccess) return hip_error(e, "hipMalloc chain weights");
-  unsigned char* base = reinterpret_cast<unsigned char*>(cp.d_blob);
-  e = hipMemcpy(base, wb.data(), wsz, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(base + wsz, bb.data(), bb.size() * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(base + wsz + bsz, kt.data(), kt.size() * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(base + wsz + bsz + ksz, i2c.data(), isz, hipMemcpyHostToDevice);
-  if (e != hipSuccess) return hip_error(e, "copy chain weights");
-  x.wblob = reinterpret_cast<const _Float16*>(base);
-  x.bblob = reinterpret_cast<const float*>(base + wsz);
-  x.ktab = reinterpret_cast<const int*>(base + wsz + bsz);
-  x.i2c_off = reinterpret_cast<const int*>(base + wsz + bsz + ksz);
-  x.i2c_n = static_cast<int>(i2c.size());
-  if (cp.lds_bytes > 64 * 1024) {  // the CU maximum: chains sharing a kernel never lower it
-    e = set_max_dynamic_lds(reinterpret_cast<const void*>(cp.xfn));
-    if (e != hipSuccess) return hip_error(e, "hipFuncSetAttribute(max dynamic LDS)");
-  }
-  cp.macs_per_img = macs;
-  od_out = od;
-  if (getenv("HBK_DEBUG_EMBED"))
-    fprintf(stderr, "hbk split chain: %d stages, in %dx%dx%d (pool %dx%d, im2col %d) -> %dx%dx%d (pool %dx%d); "
-            "G %d band %d/%d (eff %.3f), weights %s %lld B, LDS %zu B, nb %d\n",
-            x.n_stages, d.h, d.w, d.c, x.in_ph, x.in_pw, x.im2col, od.h, od.w, od.c, x.out_ph, x.out_pw, G,
-            band, od.h, efficiency(band), resident ? "LDS" : "global", (long long)w_bytes, cp.lds_bytes, nbmax);
-  return HBK_OK;
-}
-
-// The p0 pattern: [3x3 (1 -> C), 1x3 (C -> C), 3x1 (C -> C)] + output pool 2x2
-// on input width 32, C = 24, one image per source clip; all convs LeakyReLU
-// with one slope in [0, 1], or all linear. Packs the weights / biases and
-// sizes the grid; returns false (generic kernel) when the chain differs.
-constexpr int kP0W = 32, kP0C = 24;
-
-template <int kP0Band>
-bool plan_p0_band(const std::vector<OpInfo>& ops, const std::vector<int>& st, const ChainArgs& a, Dims d, Dims od,
-                  ChainPlan& cp) {
-  using P0G = P0Geo<kP0W, kP0C, kP0Band>;
-  if (st.size() != 3 || a.ipc != 1 || a.C_src != 1 || a.in_ph != 1 || a.in_pw != 1) return false;
-  if (a.out_ph != 2 || a.out_pw != 2 || d.w != kP0W || a.src_row_stride != kP0W) return false;
-  const OpInfo &o0 = ops[st[0]], &o1 = ops[st[1]], &o2 = ops[st[2]];
-  const int C = kP0C;
-  if (!(o0.kh == 3 && o0.kw == 3 && o0.cin == 1 && o0.cout == C)) return false;
-  if (!(o1.kh == 1 && o1.kw == 3 && o1.cin == C && o1.cout == C)) return false;
-  if (!(o2.kh == 3 && o2.kw == 1 && o2.cin == C && o2.cout == C)) return false;
-  const bool leaky = o0.act != 0;
-  for (const OpInfo* o : {&o0, &o1, &o2}) {
-    if ((o->act != 0) != leaky) return false;
-    if (leaky && (o->alpha != o0.alpha || !(o->alpha >= 0.f && o->alpha <= 1.f))) return false;
-  }
-  if (od.h != (d.h - 4) / 2 || od.w != (d.w - 4) / 2 || od.c != C) return false;
-  // weights: stage s = hi [32][16 ks_s] then lo; K of stage 0 = taps 0-4 | pad | taps 5-8 | pad
-  std::vector<_Float16> w(P0G::WHALFS, static_cast<_Float16>(0.f));
-  auto put = [&](int off, int ks, int n, int k, float v) {
-    uint32_t bits;
-    memcpy(&bits, &v, 4);
-    bits &= 0xFFFFE000u;
-    float hv;
-    memcpy(&hv, &bits, 4);
-    w[off + n * 16 * ks + k] = static_cast<_Float16>(hv);
-    w[off + 32 * 16 * ks + n * 16 * ks + k] = static_cast<_Float16>(v - hv);
-  };
-  for (int n = 0; n < C; ++n) {
-    for (int k = 0; k < 16; ++k) {
-      const int tap = k < 5 ? k : (k >= 8 && k < 12 ? k - 3 : -1);
-      if (tap >= 0) put(0, 1, n, k, o0.w[size_t(tap) * C + n]);
-    }
-    for (int k = 0; k < 3 * C; ++k) {
-      put(P0G::WOFF1, P0G::KS, n, k, o1.w[size_t(k) * C + n]);  // HWIO: (tap * C + ci) * C + n
-      put(P0G::WOFF2, P0G::KS, n, k, o2.w[size_t(k) * C + n]);
-    }
-  }
-  std::vector<float> b(96, 0.f);
-  for (int n = 0; n < C; ++n) {
-    b[n] = o0.b[n];
-    b[32 + n] = o1.b[n];
-    b[64 + n] = o2.b[n];
-  }
-  const size_t wbytes = (w.size() * 2 + 15) & ~size_t(15);
-  hipError_t e = hipMalloc(&cp.d_p0, wbytes + b.size() * 4);
-  if (e == hipSuccess) e = hipMemcpy(cp.d_p0, w.data(), w.size() * 2, hipMemcpyHostToDevice);
-  if (e == hipSuccess)
-    e = hipMemcpy(static_cast<unsigned char*>(cp.d_p0) + wbytes, b.data(), b.size() * 4, hipMemcpyHostToDevice);
-  cp.p0fn = leaky ? p0_chain_kernel<kP0W, kP0C, kP0Band, true> : p0_chain_kernel<kP0W, kP0C, kP0Band, false>;
-  cp.p0_lds = P0G::LDS;
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(cp.p0fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            int(cp.p0_lds));
-  int per_cu = 0;
-  if (e == hipSuccess)
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(cp.p0fn), kP0Threads,
-                                                     cp.p0_lds);
-  if (e != hipSuccess || per_cu < 1) {
-    (void)hipGetLastError();
-    if (cp.d_p0) (void)hipFree(cp.d_p0);
-    cp.d_p0 = nullptr;
-    cp.p0fn = nullptr;
-    return false;
-  }
-  cp.p0_blocks_per_cu = per_cu;
-  P0Args& p = cp.p0;
-  p.w = static_cast<const _Float16*>(cp.d_p0);
-  p.bias = reinterpret_cast<const float*>(static_cast<unsigned char*>(cp.d_p0) + wbytes);
-  p.H_in = d.h;
-  p.H_out = od.h;
-  p.n_bands = (od.h + kP0Band - 1) / kP0Band;
-  p.alpha = leaky ? o0.alpha : 0.f;
-  if (getenv("HBK_DEBUG_EMBED"))
-    fprintf(stderr, "hbk p0 chain: %dx%dx1 -> %dx%dx%d, band %d (%d bands), LDS %zu B, %d blocks/CU\n", d.h, d.w,
-            od.h, od.w, od.c, kP0Band, p.n_bands, cp.p0_lds, per_cu);
-  return true;
-}
-
-// The streaming p0 form (p0s_chain_kernel): the same chain on a 136-row input,
-// one wave per clip. Weights as plan_p0_band's (hi / lo of 16 W rounded toward
-// zero), with each stage's bias in K slot 12 (stage 0) or 72 (stages 1, 2).
-bool plan_p0s(const std::vector<OpInfo>& ops, const std::vector<int>& st, const ChainArgs& a, Dims d, Dims od,
-              ChainPlan& cp) {
-  if (getenv("HBK_EMBED_NO_P0S")) return false;
-  if (st.size() != 3 || a.ipc != 1 || a.C_src != 1 || a.in_ph != 1 || a.in_pw != 1) return false;
-  if (a.out_ph != 2 || a.out_pw != 2 || d.w != kP0W || a.src_row_stride != kP0W || d.h != kP0sRows) return false;
-  const OpInfo &o0 = ops[st[0]], &o1 = ops[st[1]], &o2 = ops[st[2]];
-  const int C = kP0C;
-  if (!(o0.kh == 3 && o0.kw == 3 && o0.cin == 1 && o0.cout == C)) return false;
-  if (!(o1.kh == 1 && o1.kw == 3 && o1.cin == C && o1.cout == C)) return false;
-  if (!(o2.kh == 3 && o2.kw == 1 && o2.cin == C && o2.cout == C)) return false;
-  const bool leaky = o0.act != 0;
-  for (const OpInfo* o : {&o0, &o1, &o2}) {
-    if ((o->act != 0) != leaky) return false;
-    if (leaky && (o->alpha != o0.alpha || !(o->alpha >= 0.f && o->alpha <= 1.f))) return false;
-  }
-  if (od.h != kP0sHout || od.w != kP0sWout || od.c != C) return false;
-  const int woff1 = 2 * 32 * 16, woff2 = woff1 + 2 * 32 * 16 * kP0sKS, total = woff2 + 2 * 32 * 16 * kP0sKS;
-  std::vector<_Float16> w(total, static_cast<_Float16>(0.f));
-  auto put = [&](int off, int ks, int n, int k, float v) {
-    uint32_t bits;
-    memcpy(&bits, &v, 4);
-    bits &= 0xFFFFE000u;
-    float hv;
-    memcpy(&hv, &bits, 4);
-    w[off + n * 16 * ks + k] = static_cast<_Float16>(hv);
-    w[off + 32 * 16 * ks + n * 16 * ks + k] = static_cast<_Float16>(v - hv);
-  };
-  for (int n = 0; n < C; ++n) {
-    // K slots (p0s_iter): lower half 0-5 = window (y, y + 1) x (dx 0-2), upper half 8-13 = window
-    // (y + 1, y + 2); taps 0-4 in the lower half, 5-8 in the upper, the bias in slot 6 (B = 1)
-    for (int k = 0; k < 16; ++k) {
-      const int tap = k < 5 ? k : (k >= 10 && k < 14 ? k - 5 : -1);
-      if (tap >= 0) put(0, 1, n, k, o0.w[size_t(tap) * C + n]);
-    }
-    put(0, 1, n, 6, o0.b[n]);
-    for (int k = 0; k < 3 * C; ++k) put(woff1, kP0sKS, n, k, o1.w[size_t(k) * C + n]);  // HWIO: (tap C + ci) C + n
-    put(woff1, kP0sKS, n, 3 * C, o1.b[n]);
-    // stage 2: K step ks, lane half h holds group (dy, c) = G2[ks][h] (p0s_iter), channels 8 c .. 8 c + 7
-    static const int G2[5][2][2] = {{{0, 0}, {0, 1}}, {{1, 0}, {1, 1}}, {{2, 0}, {2, 1}}, {{0, 2}, {1, 2}},
-                                    {{2, 2}, {-1, -1}}};
-    for (int ks = 0; ks < kP0sKS; ++ks)
-      for (int h = 0; h < 2; ++h)
-        for (int i = 0; i < 8; ++i) {
-          const int k = 16 * ks + 8 * h + i, dy = G2[ks][h][0], cg = G2[ks][h][1];
-          put(woff2, kP0sKS, n, k, dy < 0 ? (i == 0 ? o2.b[n] : 0.f) : o2.w[size_t(dy * C + 8 * cg + i) * C + n]);
-        }
-  }
-  hipError_t e = hipMalloc(&cp.d_p0, w.size() * 2);
-  if (e == hipSuccess) e = hipMemcpy(cp.d_p0, w.data(), w.size() * 2, hipMemcpyHostToDevice);
-  cp.p0fn = leaky ? p0s_chain_kernel<true> : p0s_chain_kernel<false>;
-  cp.p0_lds = kP0sLds;
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(cp.p0fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            int(cp.p0_lds));
-  int per_cu = 0;
-  if (e == hipSuccess)
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(cp.p0fn), kP0sThreads,
-                                                     cp.p0_lds);
-  if (e != hipSuccess || per_cu < 1) {
-    (void)hipGetLastError();
-    if (cp.d_p0) (void)hipFree(cp.d_p0);
-    cp.d_p0 = nullptr;
-    cp.p0fn = nullptr;
-    return false;
-  }
-  cp.p0s = true;
-  cp.p0_blocks_per_cu = per_cu;
-  P0Args& p = cp.p0;
-  p.w = static_cast<const _Float16*>(cp.d_p0);
-  p.bias = nullptr;
-  p.H_in = d.h;
-  p.H_out = od.h;
-  p.n_bands = 1;
-  p.alpha = leaky ? o0.alpha : 0.f;
-  if (getenv("HBK_DEBUG_EMBED"))
-    fprintf(stderr, "hbk p0s chain: %dx%dx1 -> %dx%dx%d, one wave per clip, LDS %zu B, %d blocks/CU\n", d.h, d.w,
-            od.h, od.w, od.c, cp.p0_lds, per_cu);
-  return true;
-}
-
-// pooled rows per task: 6 (78 KB of LDS, two blocks per CU); HBK_P0_BAND=5|7 for tuning
-bool plan_p0(const std::vector<OpInfo>& ops, const std::vector<int>& st, const ChainArgs& a, Dims d, Dims od,
-             ChainPlan& cp) {
-  if (getenv("HBK_EMBED_NO_P0")) return false;
-  if (plan_p0s(ops, st, a, d, od, cp)) return true;
-  const char* bs = getenv("HBK_P0_BAND");
-  const int band = bs ? atoi(bs) : 6;
-  if (band == 5) return plan_p0_band<5>(ops, st, a, d, od, cp);
-  if (band == 7) return plan_p0_band<7>(ops, st, a, d, od, cp);
-  return plan_p0_band<6>(ops, st, a, d, od, cp);
-}
-
-// The p1 pattern: [1x3 (CI -> 32), 3x1, 1x3, 3x1 (32 -> 32)] + output pool 2x2,
-// NHWC input of width 14 with CI = 24, one image per source image.
-constexpr int kP1W = 14, kP1CI = 24, kP1Band = 8;
-using P1G = P1Geo<kP1W, kP1CI, kP1Band>;
-
-// The streaming p1 form (p1s_chain_kernel) for a 66-row input: weights per
-// stage s as hi / lo [32][96] (K = tap * cin + ci; stage a's bias at K 72),
-// biases of stages b, c, d as [3][32] f32.
-bool plan_p1s(const std::vector<OpInfo>& ops, const std::vector<int>& st, const ChainArgs& a, Dims d, Dims od,
-              ChainPlan& cp) {
-  if (getenv("HBK_EMBED_NO_P1S")) return false;
-  if (st.size() != 4 || a.ipc != 1 || a.in_ph != 1 || a.in_pw != 1 || a.out_ph != 2 || a.out_pw != 2) return false;
-  if (d.h != kP1sHin || d.w != kP1sWi || d.c != kP1sCSI || a.C_src != kP1sCSI || a.src_row_stride != kP1sWi * kP1sCSI)
-    return false;
-  const int kh[4] = {1, 3, 1, 3}, kw[4] = {3, 1, 3, 1};
-  const bool leaky = ops[st[0]].act != 0;
-  for (int i = 0; i < 4; ++i) {
-    const OpInfo& o = ops[st[i]];
-    if (o.kh != kh[i] || o.kw != kw[i] || o.cin != (i ? kP1sCo : kP1sCSI) || o.cout != kP1sCo) return false;
-    if ((o.act != 0) != leaky) return false;
-    if (leaky && (o.alpha != ops[st[0]].alpha || !(o.alpha >= 0.f && o.alpha <= 1.f))) return false;
-  }
-  if (od.h != kP1sHout || od.w != kP1sWo || od.c != kP1sCo) return false;
-  std::vector<_Float16> w(4 * kP1sStageHalfs, static_cast<_Float16>(0.f));
-  auto put = [&](int s, int n, int k, float v) {
-    uint32_t bits;
-    memcpy(&bits, &v, 4);
-    bits &= 0xFFFFE000u;
-    float hv;
-    memcpy(&hv, &bits, 4);
-    w[s * kP1sStageHalfs + n * 96 + k] = static_cast<_Float16>(hv);
-    w[s * kP1sStageHalfs + 32 * 96 + n * 96 + k] = static_cast<_Float16>(v - hv);
-  };
-  for (int s = 0; s < 4; ++s) {
-    const OpInfo& o = ops[st[s]];
-    const int K = 3 * o.cin;
-    for (int n = 0; n < kP1sCo; ++n) {
-      for (int k = 0; k < K; ++k) put(s, n, k, o.w[size_t(k) * kP1sCo + n]);  // HWIO: (tap cin + ci) cout + n
-      if (s == 0) put(0, n, K, o.b[n]);
-    }
-  }
-  std::vector<float> b(3 * 32, 0.f);
-  for (int s = 1; s < 4; ++s)
-    for (int n = 0; n < kP1sCo; ++n) b[32 * (s - 1) + n] = ops[st[s]].b[n];
-  const size_t wbytes = (w.size() * 2 + 15) & ~size_t(15);
-  hipError_t e = hipMalloc(&cp.d_p0, wbytes + b.size() * 4);
-  if (e == hipSuccess) e = hipMemcpy(cp.d_p0, w.data(), w.size() * 2, hipMemcpyHostToDevice);
-  if (e == hipSuccess)
-    e = hipMemcpy(static_cast<unsigned char*>(cp.d_p0) + wbytes, b.data(), b.size() * 4, hipMemcpyHostToDevice);
-  cp.p1fn = leaky ? p1s_chain_kernel<true> : p1s_chain_kernel<false>;
-  cp.p0_lds = kP1sLds;
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(cp.p1fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            int(cp.p0_lds));
-  int per_cu = 0;
-  if (e == hipSuccess)
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(cp.p1fn), kP1sThreads,
-                                                     cp.p0_lds);
-  if (e != hipSuccess || per_cu < 1) {
-    (void)hipGetLastError();
-    if (cp.d_p0) (void)hipFree(cp.d_p0);
-    cp.d_p0 = nullptr;
-    cp.p1fn = nullptr;
-    return false;
-  }
-  cp.p1s = true;
-  cp.p0_blocks_per_cu = per_cu;
-  P1Args& p = cp.p1;
-  p.w = static_cast<const _Float16*>(cp.d_p0);
-  p.bias = reinterpret_cast<const float*>(static_cast<unsigned char*>(cp.d_p0) + wbytes);
-  p.H_in = d.h;
-  p.H_out = od.h;
-  p.n_bands = 1;
-  p.alpha = leaky ? ops[st[0]].alpha : 0.f;
-  if (getenv("HBK_DEBUG_EMBED"))
-    fprintf(stderr, "hbk p1s chain: %dx%dx%d -> %dx%dx%d, two-wave stage pipeline per clip, LDS %zu B, %d blocks/CU\n",
-            d.h, d.w,
-            d.c, od.h, od.w, od.c, cp.p0_lds, per_cu);
-  return true;
-}
-
-// The p2s pattern (SE20 chain 2): [1x3 (32 -> 48), 3x1, 1x3, 3x1 (48 -> 48)] on a
-// 31 x 5 x 32 input, no output pool, one image per source image. Weights hi /
-// lo [48][96] (stage a) and [48][160] (b, c, d: K = tap * 48 + ci, the bias at
-// K 144); stage a's bias as f32.
-bool plan_p2s(const std::vector<OpInfo>& ops, const std::vector<int>& st, const ChainArgs& a, Dims d, Dims od,
-              ChainPlan& cp) {
-  if (getenv("HBK_EMBED_NO_P2S")) return false;
-  if (st.size() != 4 || a.ipc != 1 || a.in_ph != 1 || a.in_pw != 1 || a.out_ph != 1 || a.out_pw != 1) return false;
-  if (d.h != kP2sHin || d.w != kP2sWi || d.c != kP2sCi || a.C_src != kP2sCi || a.src_row_stride != kP2sWi * kP2sCi)
-    return false;
-  const int kh[4] = {1, 3, 1, 3}, kw[4] = {3, 1, 3, 1};
-  const bool leaky = ops[st[0]].act != 0;
-  for (int i = 0; i < 4; ++i) {
-    const OpInfo& o = ops[st[i]];
-    if (o.kh != kh[i] || o.kw != kw[i] || o.cin != (i ? kP2sCo : kP2sCi) || o.cout != kP2sCo) return false;
-    if ((o.act != 0) != leaky) return false;
-    if (leaky && (o.alpha != ops[st[0]].alpha || !(o.alpha >= 0.f && o.alpha <= 1.f))) return false;
-  }
-  if (od.h != kP2sHout || od.w != 1 || od.c != kP2sCo) return false;
-  const size_t wa = size_t(2) * kP2sCo * kP2sKa, wsz = size_t(2) * kP2sCo * kP2sK;
-  std::vector<_Float16> w(wa + 3 * wsz, static_cast<_Float16>(0.f));
-  auto put = [&](size_t off, int Kp, int n, int k, float v) {
-    uint32_t bits;
-    memcpy(&bits, &v, 4);
-    bits &= 0xFFFFE000u;
-    float hv;
-    memcpy(&hv, &bits, 4);
-    w[off + size_t(n) * Kp + k] = static_cast<_Float16>(hv);
-    w[off + size_t(kP2sCo) * Kp + size_t(n) * Kp + k] = static_cast<_Float16>(v - hv);
-  };
-  for (int s2 = 0; s2 < 4; ++s2) {
-    const OpInfo& o = ops[st[s2]];
-    const size_t off = s2 == 0 ? 0 : wa + (s2 - 1) * wsz;
-    const int Kp = s2 == 0 ? kP2sKa : kP2sK, K = 3 * o.cin;
-    for (int n = 0; n < kP2sCo; ++n) {
-      for (int k = 0; k < K; ++k) put(off, Kp, n, k, o.w[size_t(k) * kP2sCo + n]);  // HWIO: (tap cin + ci) cout + n
-      if (s2 > 0) put(off, Kp, n, K, o.b[n]);
-    }
-  }
-  const size_t wbytes = (w.size() * 2 + 15) & ~size_t(15);
-  hipError_t e = hipMalloc(&cp.d_p0, wbytes + kP2sCo * 4);
-  if (e == hipSuccess) e = hipMemcpy(cp.d_p0, w.data(), w.size() * 2, hipMemcpyHostToDevice);
-  if (e == hipSuccess)
-    e = hipMemcpy(static_cast<unsigned char*>(cp.d_p0) + wbytes, ops[st[0]].b.data(), kP2sCo * 4,
-                  hipMemcpyHostToDevice);
-  cp.p2fn = leaky ? p2s_chain_kernel<true> : p2s_chain_kernel<false>;
-  cp.p0_lds = kP2sLds;
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(cp.p2fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            int(cp.p0_lds));
-  int per_cu = 0;
-  if (e == hipSuccess)
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(cp.p2fn), kP2sThreads,
-                                                     cp.p0_lds);
-  if (e != hipSuccess || per_cu < 1) {
-    (void)hipGetLastError();
-    if (cp.d_p0) (void)hipFree(cp.d_p0);
-    cp.d_p0 = nullptr;
-    cp.p2fn = nullptr;
-    return false;
-  }
-  cp.p0_blocks_per_cu = per_cu;
-  P2sArgs& p = cp.p2;
-  p.w = static_cast<const _Float16*>(cp.d_p0);
-  p.bias_a = reinterpret_cast<const float*>(static_cast<unsigned char*>(cp.d_p0) + wbytes);
-  p.alpha = leaky ? ops[st[0]].alpha : 0.f;
-  if (getenv("HBK_DEBUG_EMBED"))
-    fprintf(stderr, "hbk p2s chain: %dx%dx%d -> %dx%dx%d, %d clips per workgroup, LDS %zu B, %d blocks/CU\n", d.h,
-            d.w, d.c, od.h, od.w, od.c, kP2sClips, cp.p0_lds, per_cu);
-  return true;
-}
-
-// The t3s pattern (SE20's tail over its two phase images per clip): an input
-// pool 2x1 of the 27 x 1 x 48 chain-2 rows, 3x1 (48 -> 64), 1x1, 3x1, 1x1 (64),
-// 2x1 (64 -> 96), four 1x1 (96), the last without activation. Weights hi / lo
-// [cout][K] per stage (K = tap * cin + ci; stage 1 zero-padded to 160), biases f32.
-bool plan_t3s(const std::vector<OpInfo>& ops, const std::vector<int>& st, const ChainArgs& a, Dims d, Dims od,
-              ChainPlan& cp) {
-  if (getenv("HBK_EMBED_NO_T3S")) return false;
-  if (st.size() != 9 || a.ipc != 2 || a.row_off[0] != 0 || a.row_off[1] != 1 || a.in_ph != 2 || a.in_pw != 1 ||
-      a.out_ph != 1 || a.out_pw != 1)
-    return false;
-  if (d.h != kT3Hp || d.w != 1 || d.c != kT3C0 || a.C_src != kT3C0 || a.src_row_stride != kT3C0 ||
-      a.src_clip_stride != int64_t(kT3Hin) * kT3C0)
-    return false;
-  if (od.h != kT3Hout || od.w != 1 || od.c != kT3C2 || cp.x.out_img_stride != int64_t(kT3Hout) * kT3C2) return false;
-  const int kh[9] = {3, 1, 3, 1, 2, 1, 1, 1, 1};
-  const int cin[9] = {kT3C0, kT3C1, kT3C1, kT3C1, kT3C1, kT3C2, kT3C2, kT3C2, kT3C2};
-  const bool leaky = ops[st[0]].act != 0;
-  for (int i = 0; i < 9; ++i) {
-    const OpInfo& o = ops[st[i]];
-    if (o.kh != kh[i] || o.kw != 1 || o.cin != cin[i] || o.cout != (i < 4 ? kT3C1 : kT3C2)) return false;
-    if ((o.act != 0) != (leaky && i < 8)) return false;
-    if (o.act != 0 && (o.alpha != ops[st[0]].alpha || !(o.alpha >= 0.f && o.alpha <= 1.f))) return false;
-  }
-  std::vector<_Float16> w(kT3WHalfs, static_cast<_Float16>(0.f));
-  std::vector<float> b(4 * kT3C1 + 5 * kT3C2, 0.f);
-  int boff = 0;
-  for (int i = 0; i < 9; ++i) {
-    const OpInfo& o = ops[st[i]];
-    const int K = o.kh * o.cin, Kp = kT3K[i];
-    for (int n = 0; n < o.cout; ++n) {
-      for (int k = 0; k < K; ++k) {
-        const float v = o.w[size_t(k) * o.cout + n];  // HWIO: (tap cin + ci) cout + n
-        uint32_t bits;
-        memcpy(&bits, &v, 4);
-        bits &= 0xFFFFE000u;
-        float hv;
-        memcpy(&hv, &bits, 4);
-        w[kT3W[i] + size_t(n) * Kp + k] = static_cast<_Float16>(hv);
-        w[kT3W[i] + size_t(o.cout) * Kp + size_t(n) * Kp + k] = static_cast<_Float16>(v - hv);
-      }
-      b[boff + n] = o.b[n];
-    }
-    boff += o.cout;
-  }
-  const size_t wbytes = (w.size() * 2 + 15) & ~size_t(15);
-  hipError_t e = hipMalloc(&cp.d_p0, wbytes + b.size() * 4);
-  if (e == hipSuccess) e = hipMemcpy(cp.d_p0, w.data(), w.size() * 2, hipMemcpyHostToDevice);
-  if (e == hipSuccess)
-    e = hipMemcpy(static_cast<unsigned char*>(cp.d_p0) + wbytes, b.data(), b.size() * 4, hipMemcpyHostToDevice);
-  cp.t3fn = leaky ? t3s_chain_kernel<true> : t3s_chain_kernel<false>;
-  cp.p0_lds = kT3Lds;
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(cp.t3fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            int(cp.p0_lds));
-  int per_cu = 0;
-  if (e == hipSuccess)
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(cp.t3fn), kT3Threads,
-                                                     cp.p0_lds);
-  if (e != hipSuccess || per_cu < 1) {
-    (void)hipGetLastError();
-    if (cp.d_p0) (void)hipFree(cp.d_p0);
-    cp.d_p0 = nullptr;
-    cp.t3fn = nullptr;
-    return false;
-  }
-  cp.p0_blocks_per_cu = per_cu;
-  T3sArgs& p = cp.t3;
-  p.w = static_cast<const _Float16*>(cp.d_p0);
-  p.bias = reinterpret_cast<const float*>(static_cast<unsigned char*>(cp.d_p0) + wbytes);
-  p.out_img_stride = cp.x.out_img_stride;
-  p.alpha = leaky ? ops[st[0]].alpha : 0.f;
-  if (getenv("HBK_DEBUG_EMBED"))
-    fprintf(stderr, "hbk t3s chain: %dx%dx%d (pool 2x1) -> %dx%dx%d, %d images per workgroup, LDS %zu B, %d blocks/CU\n",
-            d.h, d.w, d.c, od.h, od.w, od.c, kT3Pos, cp.p0_lds, per_cu);
-  return true;
-}
-
-bool plan_p1(const std::vector<OpInfo>& ops, const std::vector<int>& st, const ChainArgs& a, Dims d, Dims od,
-             ChainPlan& cp) {
-  if (getenv("HBK_EMBED_NO_P1")) return false;
-  if (plan_p1s(ops, st, a, d, od, cp)) return true;
-  if (st.size() != 4 || a.ipc != 1 || a.in_ph != 1 || a.in_pw != 1 || a.out_ph != 2 || a.out_pw != 2) return false;
-  if (d.w != kP1W || d.c != kP1CI || a.C_src != kP1CI || a.src_row_stride != kP1W * kP1CI) return false;
-  const int C = kP1C;
-  const int kh[4] = {1, 3, 1, 3}, kw[4] = {3, 1, 3, 1};
-  bool leaky = ops[st[0]].act != 0;
-  for (int i = 0; i < 4; ++i) {
-    const OpInfo& o = ops[st[i]];
-    if (o.kh != kh[i] || o.kw != kw[i] || o.cin != (i ? C : kP1CI) || o.cout != C) return false;
-    if ((o.act != 0) != leaky) return false;
-    if (leaky && (o.alpha != ops[st[0]].alpha || !(o.alpha >= 0.f && o.alpha <= 1.f))) return false;
-  }
-  if (od.h != (d.h - 4) / 2 || od.w != (d.w - 4) / 2 || od.c != C) return false;
-  std::vector<_Float16> w(P1G::WHALFS, static_cast<_Float16>(0.f));
-  const int woff[4] = {P1G::WOFF1, P1G::WOFF2, P1G::WOFF3, P1G::WOFF4};
-  for (int i = 0; i < 4; ++i) {
-    const OpInfo& o = ops[st[i]];
-    const int ks = i ? P1G::KS : P1G::KS1, K = 3 * o.cin;
-    for (int n = 0; n < C; ++n)
-      for (int k = 0; k < K; ++k) {
-        const float v = o.w[size_t(k) * C + n];  // HWIO: (tap * cin + ci) * cout + n
-        uint32_t bits;
-        memcpy(&bits, &v, 4);
-        bits &= 0xFFFFE000u;
-        float hv;
-        memcpy(&hv, &bits, 4);
-        w[woff[i] + n * 16 * ks + k] = static_cast<_Float16>(hv);
-        w[woff[i] + 32 * 16 * ks + n * 16 * ks + k] = static_cast<_Float16>(v - hv);
-      }
-  }
-  std::vector<float> b(128, 0.f);
-  for (int i = 0; i < 4; ++i)
-    for (int n = 0; n < C; ++n) b[32 * i + n] = ops[st[i]].b[n];
-  const size_t wbytes = (w.size() * 2 + 15) & ~size_t(15);
-  hipError_t e = hipMalloc(&cp.d_p0, wbytes + b.size() * 4);
-  if (e == hipSuccess) e = hipMemcpy(cp.d_p0, w.data(), w.size() * 2, hipMemcpyHostToDevice);
-  if (e == hipSuccess)
-    e = hipMemcpy(static_cast<unsigned char*>(cp.d_p0) + wbytes, b.data(), b.size() * 4, hipMemcpyHostToDevice);
-  cp.p1fn = leaky ? p1_chain_kernel<kP1W, kP1CI, kP1Band, true> : p1_chain_kernel<kP1W, kP1CI, kP1Band, false>;
-  cp.p0_lds = P1G::LDS;
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(cp.p1fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            int(cp.p0_lds));
-  int per_cu = 0;
-  if (e == hipSuccess)
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(cp.p1fn), kP0Threads,
-                                                     cp.p0_lds);
-  if (e != hipSuccess || per_cu < 1) {
-    (void)hipGetLastError();
-    if (cp.d_p0) (void)hipFree(cp.d_p0);
-    cp.d_p0 = nullptr;
-    cp.p1fn = nullptr;
-    return false;
-  }
-  cp.p0_blocks_per_cu = per_cu;
-  P1Args& p = cp.p1;
-  p.w = static_cast<const _Float16*>(cp.d_p0);
-  p.bias = reinterpret_cast<const float*>(static_cast<unsigned char*>(cp.d_p0) + wbytes);
-  p.H_in = d.h;
-  p.H_out = od.h;
-  p.n_bands = (od.h + kP1Band - 1) / kP1Band;
-  p.alpha = leaky ? ops[st[0]].alpha : 0.f;
-  if (getenv("HBK_DEBUG_EMBED"))
-    fprintf(stderr, "hbk p1 chain: %dx%dx%d -> %dx%dx%d, band %d (%d bands), LDS %zu B, %d blocks/CU\n", d.h, d.w,
-            d.c, od.h, od.w, od.c, kP1Band, p.n_bands, cp.p0_lds, per_cu);
-  return true;
-}
-
-// Builds the chains for ops [o0, o1) applied to images of dims `in`, reading
-// image i from row_off[i % ipc] of source clip i / ipc.
-int build_segment(const std::vector<OpInfo>& ops, int o0, int o1, Dims in, int ipc,
-                  const std::vector<int>& row_off, int64_t src_clip_floats, int src_row_floats,
-                  int first_src_buf, bool split, Program& prog, std::vector<Dims>* out_dims_per_chain) {
-  int i = o0;
-  Dims cur = in;
-  int src_buf = first_src_buf;
-  bool first = true;
-  while (i < o1) {
-    ChainPlan cp;
-    ChainArgs& a = cp.args;
-    a.ipc = first ? ipc : 1;
-    for (int k = 0; k < kMaxWin; ++k) a.row_off[k] = 0;
-    if (first)
-      for (size_t k = 0; k < row_off.size(); ++k) a.row_off[k] = row_off[k];
-    a.src_clip_stride = first ? src_clip_floats : int64_t(cur.h) * cur.w * cur.c;
-    a.src_row_stride = first ? src_row_floats : cur.w * cur.c;
-    a.C_src = cur.c;
-    a.in_ph = a.in_pw = 1;
-    if (ops[i].kind == HBK_OP_MAXPOOL) {
-      a.in_ph = ops[i].kh;
-      a.in_pw = ops[i].kw;
-      ++i;
-    }
-    Dims d{cur.h / a.in_ph, cur.w / a.in_pw, cur.c};
-    a.W_in = d.w;
-    const int H_in = d.h;
-    std::vector<int> stage_ops;
-    while (i < o1 && ops[i].kind == HBK_OP_CONV && int(stage_ops.size()) < kMaxStages) {
-      stage_ops.push_back(i);
-      ++i;
-    }
-    if (stage_ops.empty()) {
-      set_error("hbk: unsupported graph: a max-pool must be followed by a conv");
-      return HBK_ERR_UNSUPPORTED;
-    }
-    a.out_ph = a.out_pw = 1;
-    if (i < o1 && ops[i].kind == HBK_OP_MAXPOOL && (i + 1 >= o1 || ops[i + 1].kind == HBK_OP_CONV)) {
-      // keep the pool as this chain's output pool unless the next chain needs it as input pool
-      a.out_ph = ops[i].kh;
-      a.out_pw = ops[i].kw;
-      ++i;
-    }
-    if (split) {
-      Dims od;
-      const int rc = layout_split(ops, stage_ops, d, a, cp, od);
-      if (rc) return rc;
-      if (!plan_p0(ops, stage_ops, a, d, od, cp) && !plan_p1(ops, stage_ops, a, d, od, cp) &&
-          !plan_p2s(ops, stage_ops, a, d, od, cp))
-        plan_t3s(ops, stage_ops, a, d, od, cp);
-      cp.x.dbg_slot = static_cast<int>(prog.chains.size() % 4);
-      if (const char* e = getenv("HBK_DEBUG_SKIP")) cp.x.dbg_skip = atoi(e);
-      cp.src_buf = src_buf;
-      cp.out_floats = cp.x.out_img_stride * (first ? ipc : 1);
-      prog.chains.push_back(cp);
-      if (out_dims_per_chain) out_dims_per_chain->push_back(od);
-      src_buf = -2;
-      cur = od;
-      first = false;
-      continue;
-    }
-    // stages
-    int nb = 1;
-    int cin = d.c, h = H_in, w = d.w;
-    a.n_stages = static_cast<int>(stage_ops.size());
-    a.shrink = 0;
-    double macs = 0;
-    std::vector<Dims> tens;  // stage input/output tensors (per image, padded channels)
-    for (int s = 0; s < a.n_stages; ++s) {
-      const OpInfo& op = ops[stage_ops[s]];
-      if (op.cin != cin) {
-        set_error("hbk: graph channel mismatch at op %d (%d != %d)", stage_ops[s], op.cin, cin);
-        return HBK_ERR_ARG;
-      }
-      StageDesc& S = a.st[s];
-      S.kh = op.kh;
-      S.kw = op.kw;
-      S.cin = op.cin;
-      S.cinp = odd_pad(op.cin);
-      S.cout = op.cout;
-      S.coutp = odd_pad(op.cout);
-      S.K = op.kh * op.kw * op.cin;
-      S.ksteps = (S.K + 3) / 4;
-      S.act = op.act;
-      S.alpha = op.alpha;
-      nb = std::max(nb, (op.cout + 15) / 16);
-      a.shrink += op.kh - 1;
-      h -= op.kh - 1;
-      w -= op.kw - 1;
-      if (h <= 0 || w <= 0) {
-        set_error("hbk: graph collapses the image at op %d", stage_ops[s]);
-        return HBK_ERR_ARG;
-      }
-      macs += double(h) * w * op.cout * S.K;
-      cin = op.cout;
-    }
-    cp.nb = nb;  // > 6 blocks: the 6-block kernel loops over channel groups
-    a.wstride = nb * 16 + ((nb * 16) % 32 == 0 ? 16 : 0);  // kq rows on different bank halves
-    // pack weights: per stage [ksteps*4][wstride] then bias [nb*16]
-    std::vector<float> blob;
-    int max_stage_w = 0, max_k = 0;
-    for (int s = 0; s < a.n_stages; ++s) {
-      const OpInfo& op = ops[stage_ops[s]];
-      StageDesc& S = a.st[s];
-      S.w_off = static_cast<int>(blob.size());
-      const int rows = S.ksteps * 4;
-      blob.resize(blob.size() + size_t(rows) * a.wstride, 0.f);
-      for (int k = 0; k < S.K; ++k)
-        for (int n = 0; n < op.cout; ++n) blob[S.w_off + size_t(k) * a.wstride + n] = op.w[size_t(k) * op.cout + n];
-      max_stage_w = std::max(max_stage_w, rows * a.wstride);
-      max_k = std::max(max_k, rows);
-    }
-    for (int s = 0; s < a.n_stages; ++s) {
-      const OpInfo& op = ops[stage_ops[s]];
-      a.st[s].b_off = static_cast<int>(blob.size());
-      for (int n = 0; n < nb * 16; ++n) blob.push_back(n < op.cout ? op.b[n] : 0.f);
-    }
-    a.wblob_floats = static_cast<int>(blob.size());
-    // output dims
-    Dims od{h / a.out_ph, w / a.out_pw, cin};
-    a.H_out = od.h;
-    a.W_out = od.w;
-    a.C_out = od.c;
-    a.out_img_stride = int64_t(od.h) * od.w * od.c;
-    if (od.h <= 0 || od.w <= 0) {
-      set_error("hbk: pooling collapses the image");
-      return HBK_ERR_ARG;
-    }
-    // choose G (images per task) and band (output rows per task) for the LDS budget
-    auto lds_floats = [&](int G, int band, bool resident) -> int64_t {
-      int rows = band * a.out_ph;  // rows of the last conv output
-      std::vector<int64_t> t(a.n_stages + 1);
-      for (int s = a.n_stages - 1; s >= 0; --s) {
-        const StageDesc& S = a.st[s];
-        int wo = d.w;
-        for (int q = 0; q <= s; ++q) wo -= a.st[q].kw - 1;
-        t[s + 1] = int64_t(G) * rows * wo * S.coutp;
-        rows += S.kh - 1;
-      }
-      t[0] = int64_t(G) * rows * d.w * a.st[0].cinp;
-      int64_t x = 0, y = 0;
-      for (int s = 0; s <= a.n_stages; ++s) (s % 2 == 0 ? x : y) = std::max(s % 2 == 0 ? x : y, t[s]);
-      int64_t wf = resident ? a.wblob_floats : 0;
-      return ((x + 3) & ~3) + ((y + 3) & ~3) + ((wf + 3) & ~3) + ((max_k + 3) & ~3);
-    };
-    const int64_t budget = kLdsBudget / 4;
-    bool resident = lds_floats(1, 1, true) <= budget;
-    int band = 0, G = 1;
-    for (int b = od.h; b >= 1; --b)
-      if (lds_floats(1, b, resident) <= budget) { band = b; break; }
-    if (band == 0) {
-      set_error("hbk: one output row of a chain does not fit in LDS");
-      return HBK_ERR_UNSUPPORTED;
-    }
-    if (band == od.h)
-      while (G < 64 && lds_floats(G * 2, band, resident) <= budget) G *= 2;
-    a.G = G;
-    a.band = band;
-    a.n_bands = (od.h + band - 1) / band;
-    int64_t xf = 0, yf = 0;
-    {
-      int rows = band * a.out_ph;
-      std::vector<int64_t> t(a.n_stages + 1);
-      for (int s = a.n_stages - 1; s >= 0; --s) {
-        int wo = d.w;
-        for (int q = 0; q <= s; ++q) wo -= a.st[q].kw - 1;
-        t[s + 1] = int64_t(G) * rows * wo * a.st[s].coutp;
-        rows += a.st[s].kh - 1;
-      }
-      t[0] = int64_t(G) * rows * d.w * a.st[0].cinp;
-      for (int s = 0; s <= a.n_stages; ++s) (s % 2 == 0 ? xf : yf) = std::max(s % 2 == 0 ? xf : yf, t[s]);
-    }
-    a.lds_x = 0;
-    a.lds_y = static_cast<int>((xf + 3) & ~3);
-    a.lds_w = a.lds_y + static_cast<int>((yf + 3) & ~3);
-    a.lds_k = a.lds_w + (resident ? ((a.wblob_floats + 3) & ~3) : 0);
-    cp.lds_bytes = size_t(a.lds_k + ((max_k + 3) & ~3)) * 4;
-    cp.wg = !resident;
-    cp.fn = pick_kernel(nb, cp.wg);
-    (void)max_stage_w;
-    // device weights
-    hipError_t e = hipMalloc(&cp.d_blob, blob.size() * sizeof(float));
-    if (e != hipSuccess) return hip_error(e, "hipMalloc chain weights");
-    e = hipMemcpy(cp.d_blob, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return hip_error(e, "copy chain weights");
-    a.wblob = cp.d_blob;
-    if (cp.lds_bytes > 64 * 1024) {
-      e = set_max_dynamic_lds(reinterpret_cast<const void*>(cp.fn));  // see layout_split
-      if (e != hipSuccess) return hip_error(e, "hipFuncSetAttribute(max dynamic LDS)");
-    }
-    cp.macs_per_img = macs;
-    cp.src_buf = src_buf;
-    cp.out_floats = a.out_img_stride * (first ? ipc : 1);
-    prog.chains.push_back(cp);
-    if (out_dims_per_chain) out_dims_per_chain->push_back(od);
-    src_buf = -2;  // placeholder: assigned by the caller
-    cur = od;
-    first = false;
-  }
-  return HBK_OK;
-}
-
-// Assign ping-pong workspace buffers: chain k writes buffer k % 2, the last
-// writes the call's output; record per-unit buffer sizes.
-void assign_buffers(Program& prog, int64_t units_per_first_img_ratio) {
-  (void)units_per_first_img_ratio;
-  const size_t n = prog.chains.size();
-  for (size_t k = 0; k < n; ++k) {
-    ChainPlan& c = prog.chains[k];
-    c.src_buf = (k == 0) ? -1 : int((k - 1) % 2);
-    c.dst_buf = (k + 1 == n && prog.gather_src.empty()) ? -1 : int(k % 2);
-  }
-  if (!prog.gather_src.empty()) prog.gather_buf = int((n - 1) % 2);
-}
 
 // out[u][i][:] = src[u][gather_src[i]][:] (rows of `row` floats, row % 4 == 0);
 // one wave per unit, all of a unit's reads ahead of its writes (distinct buffers)
@@ -3564,141 +2292,244 @@ __global__ void __launch_bounds__(256) embed_gather_kernel(const float* __restri
   }
 }
 
+// The one reader of the planning knobs, called at every plan creation
+// (HBK_EMBED_CHUNK is latched per process in chunk_clips).
+EmbedKnobs read_embed_knobs() {
+  EmbedKnobs k;
+  if (const char* e = getenv("HBK_EMBED_LDS_KB")) {
+    k.lds_kb_set = true;
+    k.lds_kb = atoi(e);
+  }
+  if (const char* e = getenv("HBK_EMBED_WEIGHTS")) k.weights = !strcmp(e, "lds") ? 1 : !strcmp(e, "global") ? 2 : 0;
+  k.no_p0 = getenv("HBK_EMBED_NO_P0") != nullptr;
+  k.no_p0s = getenv("HBK_EMBED_NO_P0S") != nullptr;
+  k.no_p1 = getenv("HBK_EMBED_NO_P1") != nullptr;
+  k.no_p1s = getenv("HBK_EMBED_NO_P1S") != nullptr;
+  k.no_p2s = getenv("HBK_EMBED_NO_P2S") != nullptr;
+  k.no_t3s = getenv("HBK_EMBED_NO_T3S") != nullptr;
+  k.no_dedup = getenv("HBK_EMBED_NO_DEDUP") != nullptr;
+  if (const char* e = getenv("HBK_P0_BAND")) k.p0_band = atoi(e);
+  k.debug = getenv("HBK_DEBUG_EMBED") != nullptr;
+  if (const char* e = getenv("HBK_DEBUG_SKIP")) k.debug_skip = atoi(e);
+  return k;
+}
+
+template <class A>
+const void* addr(void (*kernel)(A)) {
+  return reinterpret_cast<const void*>(kernel);
+}
+
+// The kernel that a KernelChoice names.
+const void* kernel_address(KernelChoice k) {
+  const bool f = k.flag;
+  switch (k.kind) {
+    case Kern::exact:  // RB x NB accumulators of 4 VGPRs: keep RB * NB <= 12
+      switch (k.n) {
+        case 1: return f ? addr(conv_chain_kernel<1, 4, true>) : addr(conv_chain_kernel<1, 4, false>);
+        case 2: return f ? addr(conv_chain_kernel<2, 4, true>) : addr(conv_chain_kernel<2, 4, false>);
+        case 3: return f ? addr(conv_chain_kernel<3, 4, true>) : addr(conv_chain_kernel<3, 4, false>);
+        case 4: return f ? addr(conv_chain_kernel<4, 2, true>) : addr(conv_chain_kernel<4, 2, false>);
+        case 5: return f ? addr(conv_chain_kernel<5, 2, true>) : addr(conv_chain_kernel<5, 2, false>);
+        default: return f ? addr(conv_chain_kernel<6, 2, true>) : addr(conv_chain_kernel<6, 2, false>);
+      }
+    case Kern::x3:
+      switch (k.n) {
+        case 1: return f ? addr(conv_chain_x3_kernel<1, true>) : addr(conv_chain_x3_kernel<1, false>);
+        case 2: return f ? addr(conv_chain_x3_kernel<2, true>) : addr(conv_chain_x3_kernel<2, false>);
+        case 3: return f ? addr(conv_chain_x3_kernel<3, true>) : addr(conv_chain_x3_kernel<3, false>);
+        default: return f ? addr(conv_chain_x3_kernel<4, true>) : addr(conv_chain_x3_kernel<4, false>);  // > 3 blocks: groups of 3
+      }
+    case Kern::p0_band:
+      switch (k.n) {
+        case 5: return f ? addr(p0_chain_kernel<kP0W, kP0C, 5, true>) : addr(p0_chain_kernel<kP0W, kP0C, 5, false>);
+        case 7: return f ? addr(p0_chain_kernel<kP0W, kP0C, 7, true>) : addr(p0_chain_kernel<kP0W, kP0C, 7, false>);
+        default: return f ? addr(p0_chain_kernel<kP0W, kP0C, 6, true>) : addr(p0_chain_kernel<kP0W, kP0C, 6, false>);
+      }
+    case Kern::p0s: return f ? addr(p0s_chain_kernel<true>) : addr(p0s_chain_kernel<false>);
+    case Kern::p1:
+      return f ? addr(p1_chain_kernel<kP1W, kP1CI, kP1Band, true>) : addr(p1_chain_kernel<kP1W, kP1CI, kP1Band, false>);
+    case Kern::p1s: return f ? addr(p1s_chain_kernel<true>) : addr(p1s_chain_kernel<false>);
+    case Kern::p2s: return f ? addr(p2s_chain_kernel<true>) : addr(p2s_chain_kernel<false>);
+    case Kern::t3s: return f ? addr(t3s_chain_kernel<true>) : addr(t3s_chain_kernel<false>);
+  }
+  return nullptr;
+}
+
+// Dynamic-LDS limit of a kernel raised to what the CU holds beside its static
+// LDS (set once to the maximum, so plans sharing the kernel never lower it).
+hipError_t set_max_dynamic_lds(const void* fn) {
+  hipFuncAttributes at;
+  hipError_t e = hipFuncGetAttributes(&at, fn);
+  if (e != hipSuccess) return e;
+  return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
+                             int(160 * 1024 - static_cast<int>(at.sharedSizeBytes)));
+}
+
+// The blob's addresses in the argument struct (Launch::ptr_off).
+void set_pointers(ChainArgs& a, const Launch&, const unsigned char* blob) {
+  a.wblob = reinterpret_cast<const float*>(blob);
+}
+void set_pointers(XArgs& x, const Launch& L, const unsigned char* blob) {
+  x.wblob = reinterpret_cast<const _Float16*>(blob);
+  x.bblob = reinterpret_cast<const float*>(blob + L.ptr_off[1]);
+  x.ktab = reinterpret_cast<const int*>(blob + L.ptr_off[2]);
+  x.i2c_off = reinterpret_cast<const int*>(blob + L.ptr_off[3]);
+}
+template <class A>
+void set_pointers(A& p, const Launch& L, const unsigned char* blob) {  // the pattern kernels
+  p.w = reinterpret_cast<const _Float16*>(blob);
+  if (L.ptr_off[1] >= L.blob.size()) return;  // (p0s: its biases ride in the weights)
+  const float* bias = reinterpret_cast<const float*>(blob + L.ptr_off[1]);
+  if constexpr (std::is_same_v<A, P2sArgs>) p.bias_a = bias;
+  else p.bias = bias;
+}
+
+// Uploads a Launch's bytes, points its arguments at them, resolves its kernel,
+// raises the kernel's dynamic-LDS limit and prints the debug line. A pattern
+// kernel whose upload, attribute or occupancy call fails is dropped silently
+// (its slot stays empty and the chain runs on its generic kernel).
+int realise(const Launch& L, bool pattern, bool debug, Slot& s) {
+  const void* fn = kernel_address(L.kernel);
+  hipError_t e = hipMalloc(&s.d_blob, L.blob.size());
+  if (e != hipSuccess && !pattern) return hip_error(e, "hipMalloc chain weights");
+  if (e == hipSuccess) e = hipMemcpy(s.d_blob, L.blob.data(), L.blob.size(), hipMemcpyHostToDevice);
+  if (e != hipSuccess && !pattern) return hip_error(e, "copy chain weights");
+  if (pattern) {
+    if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, int(L.lds_bytes));
+    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&s.blocks_per_cu, fn, L.threads, L.lds_bytes);
+    if (e != hipSuccess || s.blocks_per_cu < 1) {
+      (void)hipGetLastError();
+      if (s.d_blob) (void)hipFree(s.d_blob);
+      s.d_blob = nullptr;
+      return HBK_OK;
+    }
+  } else {
+    if (L.lds_bytes > 64 * 1024) {  // the CU maximum: chains sharing a kernel never lower it
+      e = set_max_dynamic_lds(fn);
+      if (e != hipSuccess) return hip_error(e, "hipFuncSetAttribute(max dynamic LDS)");
+    }
+    s.blocks_per_cu = L.kernel.kind == Kern::exact
+                          ? 2
+                          : std::max<int>(1, std::min<int>(4, int((160 * 1024) / std::max<size_t>(L.lds_bytes, 1))));
+  }
+  s.plan = &L;
+  s.fn = fn;
+  s.args = L.args;
+  std::visit([&](auto& a) { set_pointers(a, L, static_cast<const unsigned char*>(s.d_blob)); }, s.args);
+  if (debug && pattern) fprintf(stderr, "%s, %d blocks/CU\n", L.debug.c_str(), s.blocks_per_cu);
+  if (debug && !pattern) fputs(L.debug.c_str(), stderr);
+  return HBK_OK;
+}
+
+int realise_program(const ProgramPlan& prog, bool debug, std::vector<ChainPlan>& dev) {
+  dev.resize(prog.chains.size());  // (all slots exist before the first allocation: destroy frees what was made)
+  for (size_t k = 0; k < dev.size(); ++k) {
+    const int rc = realise(prog.chains[k].base, false, debug, dev[k].base);
+    if (rc) return rc;
+    if (prog.chains[k].pattern) realise(*prog.chains[k].pattern, true, debug, dev[k].pattern);
+  }
+  return HBK_OK;
+}
+
+// The per-call fields of an argument struct.
+void bind(ChainArgs& a, const float* in, int64_t stride, float* out, int64_t n_img, int*) {
+  a.in = in;
+  a.src_clip_stride = stride;
+  a.out = out;
+  a.n_img = n_img;
+}
+void bind(XArgs& x, const float* in, int64_t stride, float* out, int64_t n_img, int* range_flag) {
+  x.range_flag = range_flag;
+  x.in = in;
+  x.src_clip_stride = stride;
+  x.out = out;
+  if ((reinterpret_cast<uintptr_t>(x.out) & 15) || (x.out_img_stride & 3)) x.vec_out = 0;
+  if ((reinterpret_cast<uintptr_t>(x.in) & 15) || (x.src_clip_stride & 3) || (x.src_row_stride & 3)) x.raw_vec = 0;
+  x.n_img = n_img;
+}
+template <class A>
+void bind(A& p, const float* in, int64_t stride, float* out, int64_t n_img, int* range_flag) {  // the pattern kernels
+  p.range_flag = range_flag;
+  p.in = in;
+  if constexpr (std::is_same_v<A, T3sArgs>) p.src_clip_stride = stride;
+  else p.src_img_stride = stride;
+  p.out = out;
+  p.n_img = n_img;
+}
+
 // Runs chains [k_begin, k_end) of the program (k_end < 0: to the end). The
 // first chain run reads `in` (the call's input, or for k_begin > 0 the output
 // of chain k_begin - 1 in its workspace layout); the last writes `out` (for
 // k_end < n: chain k_end - 1's output in its workspace layout, no gather).
-int run_program(const Program& prog, const float* in, int64_t n_units, int64_t in_unit_stride,
-                float* out, int64_t out_unit_floats, float* ws, int64_t chunk, hipStream_t stream,
-                const std::vector<int64_t>& imgs_per_unit, const std::vector<int64_t>& buf_unit_floats,
-                int* range_flag, int k_begin = 0, int k_end = -1) {
+// A chain runs on its pattern kernel when the buffers allow it, else on its
+// generic kernel (split-f16 x3 or exact f32).
+int run_program(const ProgramPlan& prog, const std::vector<ChainPlan>& dev, const int* d_gather, const float* in,
+                int64_t n_units, int64_t in_unit_stride, float* out, int64_t out_unit_floats, float* ws,
+                int64_t chunk, hipStream_t stream, int* range_flag, int k_begin = 0, int k_end = -1) {
   const int n_ch = static_cast<int>(prog.chains.size());
   if (k_end < 0) k_end = n_ch;
   for (int64_t u0 = 0; u0 < n_units; u0 += chunk) {
     const int64_t nu = std::min(chunk, n_units - u0);
-    float* bufs[2] = {ws, ws + chunk * buf_unit_floats[0]};
+    float* bufs[2] = {ws, ws + chunk * prog.buf_floats[0]};
     for (int k = k_begin; k < k_end; ++k) {
-      ChainPlan c = prog.chains[k];
-      if (k == k_begin && k_begin > 0) c.src_buf = -1;  // the caller's copy of chain k - 1's output
-      if (k == k_end - 1 && k_end < n_ch) c.dst_buf = -1;  // handed to the caller (no gather)
-      if (c.p0fn) {
-        P0Args pa = c.p0;
-        pa.range_flag = range_flag;
-        pa.in = c.src_buf < 0 ? in + u0 * in_unit_stride : bufs[c.src_buf];
-        pa.src_img_stride = c.src_buf < 0 ? in_unit_stride : c.x.src_clip_stride;  // (in_unit_stride == it past chain 0)
-        pa.out = c.dst_buf < 0 ? out + u0 * out_unit_floats : bufs[c.dst_buf];
-        pa.n_img = nu * imgs_per_unit[k];
-        const bool aligned = !(reinterpret_cast<uintptr_t>(pa.in) & 15) && !(pa.src_img_stride & 3) &&
-                             !(reinterpret_cast<uintptr_t>(pa.out) & 15);
-        if (aligned && pa.n_img * pa.n_bands < (int64_t(1) << 31)) {
-          const int64_t tasks = c.p0s ? (pa.n_img + kP0sWaves - 1) / kP0sWaves : pa.n_img * pa.n_bands;
-          const int64_t blocks = std::min<int64_t>(tasks, persistent_blocks(c.p0_blocks_per_cu, stream));
-          if (blocks <= 0) continue;
-          hipLaunchKernelGGL(c.p0fn, dim3(unsigned(blocks)), dim3(kP0Threads), c.p0_lds, stream, pa);
-          HBK_LAUNCH_CHECK("p0_chain_kernel");
-          continue;
+      const ChainHost& h = prog.chains[k];
+      const int src_buf = (k == k_begin && k_begin > 0) ? -1 : h.src_buf;  // the caller's copy of chain k - 1's output
+      const int dst_buf = (k == k_end - 1 && k_end < n_ch) ? -1 : h.dst_buf;  // handed to the caller (no gather)
+      const float* src = src_buf < 0 ? in + u0 * in_unit_stride : bufs[src_buf];
+      const int64_t stride = src_buf < 0 ? in_unit_stride : h.src_clip_stride;
+      float* dst = dst_buf < 0 ? out + u0 * out_unit_floats : bufs[dst_buf];
+      const int64_t n_img = nu * h.imgs_per_unit;
+      for (const Slot* s : {&dev[k].pattern, &dev[k].base}) {
+        if (!s->fn) continue;
+        const Launch& L = *s->plan;
+        if (s == &dev[k].pattern) {
+          const bool aligned = !(reinterpret_cast<uintptr_t>(src) & 15) && !(stride & 3) &&
+                               !(reinterpret_cast<uintptr_t>(dst) & 15) && !(L.out_stride_4 & 3);
+          if (!aligned || stride < L.min_src_stride) continue;
+          if (L.tasks_below_2_31 && n_img * L.n_bands >= (int64_t(1) << 31)) continue;
         }
-      }
-      if (c.p1fn) {
-        P1Args pa = c.p1;
-        pa.range_flag = range_flag;
-        pa.in = c.src_buf < 0 ? in + u0 * in_unit_stride : bufs[c.src_buf];
-        pa.src_img_stride = c.src_buf < 0 ? in_unit_stride : c.x.src_clip_stride;  // (in_unit_stride == it past chain 0)
-        pa.out = c.dst_buf < 0 ? out + u0 * out_unit_floats : bufs[c.dst_buf];
-        pa.n_img = nu * imgs_per_unit[k];
-        const bool aligned = !(reinterpret_cast<uintptr_t>(pa.in) & 15) && !(pa.src_img_stride & 3) &&
-                             !(reinterpret_cast<uintptr_t>(pa.out) & 15);
-        if (aligned && pa.n_img * pa.n_bands < (int64_t(1) << 31)) {
-          const int64_t tasks = c.p1s ? pa.n_img : pa.n_img * pa.n_bands;
-          const int64_t blocks = std::min<int64_t>(tasks, persistent_blocks(c.p0_blocks_per_cu, stream));
-          if (blocks <= 0) continue;
-          hipLaunchKernelGGL(c.p1fn, dim3(unsigned(blocks)), dim3(c.p1s ? kP1sThreads : kP0Threads), c.p0_lds, stream, pa);
-          HBK_LAUNCH_CHECK("p1_chain_kernel");
-          continue;
+        KernelArgs args = s->args;
+        void* argp = std::visit(
+            [&](auto& a) -> void* {
+              bind(a, src, stride, dst, n_img, range_flag);
+              return &a;
+            },
+            args);
+        const int64_t tasks = ((n_img + L.imgs_per_task - 1) / L.imgs_per_task) * L.n_bands;
+        const int64_t blocks = std::min<int64_t>(tasks, persistent_blocks(s->blocks_per_cu, stream));
+        if (blocks > 0) {
+          (void)hipLaunchKernel(s->fn, dim3(unsigned(blocks)), dim3(L.threads), &argp, L.lds_bytes, stream);
+          HBK_LAUNCH_CHECK(L.name);
         }
+        break;
       }
-      if (c.p2fn) {
-        P2sArgs pa = c.p2;
-        pa.range_flag = range_flag;
-        pa.in = c.src_buf < 0 ? in + u0 * in_unit_stride : bufs[c.src_buf];
-        pa.src_img_stride = c.src_buf < 0 ? in_unit_stride : c.x.src_clip_stride;  // (in_unit_stride == it past chain 0)
-        pa.out = c.dst_buf < 0 ? out + u0 * out_unit_floats : bufs[c.dst_buf];
-        pa.n_img = nu * imgs_per_unit[k];
-        const bool aligned = !(reinterpret_cast<uintptr_t>(pa.in) & 15) && !(pa.src_img_stride & 3) &&
-                             !(reinterpret_cast<uintptr_t>(pa.out) & 15);
-        if (aligned) {
-          const int64_t groups = (pa.n_img + kP2sClips - 1) / kP2sClips;
-          const int64_t blocks = std::min<int64_t>(groups, persistent_blocks(c.p0_blocks_per_cu, stream));
-          if (blocks <= 0) continue;
-          hipLaunchKernelGGL(c.p2fn, dim3(unsigned(blocks)), dim3(kP2sThreads), c.p0_lds, stream, pa);
-          HBK_LAUNCH_CHECK("p2s_chain_kernel");
-          continue;
-        }
-      }
-      if (c.t3fn) {
-        T3sArgs pa = c.t3;
-        pa.range_flag = range_flag;
-        pa.in = c.src_buf < 0 ? in + u0 * in_unit_stride : bufs[c.src_buf];
-        pa.src_clip_stride = c.src_buf < 0 ? in_unit_stride : c.x.src_clip_stride;
-        pa.out = c.dst_buf < 0 ? out + u0 * out_unit_floats : bufs[c.dst_buf];
-        pa.n_img = nu * imgs_per_unit[k];
-        const bool aligned = !(reinterpret_cast<uintptr_t>(pa.in) & 15) && !(pa.src_clip_stride & 3) &&
-                             !(reinterpret_cast<uintptr_t>(pa.out) & 15) && !(pa.out_img_stride & 3);
-        if (aligned && pa.src_clip_stride >= int64_t(kT3Hin) * kT3C0) {
-          const int64_t groups = (pa.n_img + kT3Pos - 1) / kT3Pos;
-          const int64_t blocks = std::min<int64_t>(groups, persistent_blocks(c.p0_blocks_per_cu, stream));
-          if (blocks <= 0) continue;
-          hipLaunchKernelGGL(c.t3fn, dim3(unsigned(blocks)), dim3(kT3Threads), c.p0_lds, stream, pa);
-          HBK_LAUNCH_CHECK("t3s_chain_kernel");
-          continue;
-        }
-      }
-      if (c.split) {
-        XArgs x = c.x;
-        x.range_flag = range_flag;
-        if (c.src_buf < 0) {
-          x.in = in + u0 * in_unit_stride;
-          x.src_clip_stride = in_unit_stride;
-        } else {
-          x.in = bufs[c.src_buf];
-        }
-        x.out = c.dst_buf < 0 ? out + u0 * out_unit_floats : bufs[c.dst_buf];
-        if ((reinterpret_cast<uintptr_t>(x.out) & 15) || (x.out_img_stride & 3)) x.vec_out = 0;
-        if ((reinterpret_cast<uintptr_t>(x.in) & 15) || (x.src_clip_stride & 3) || (x.src_row_stride & 3))
-          x.raw_vec = 0;
-        x.n_img = nu * imgs_per_unit[k];
-        const int64_t tasks = ((x.n_img + x.G - 1) / x.G) * x.n_bands;
-        const int per_cu = std::max<int>(1, std::min<int>(4, int((160 * 1024) / std::max<size_t>(c.lds_bytes, 1))));
-        const int64_t blocks = std::min<int64_t>(tasks, persistent_blocks(per_cu, stream));
-        if (blocks <= 0) continue;
-        hipLaunchKernelGGL(c.xfn, dim3(unsigned(blocks)), dim3(kXThreads), c.lds_bytes, stream, x);
-        HBK_LAUNCH_CHECK("conv_chain_x3_kernel");
-        continue;
-      }
-      ChainArgs a = c.args;
-      if (c.src_buf < 0) {
-        a.in = in + u0 * in_unit_stride;
-        a.src_clip_stride = in_unit_stride;
-      } else {
-        a.in = bufs[c.src_buf];
-      }
-      a.out = c.dst_buf < 0 ? out + u0 * out_unit_floats : bufs[c.dst_buf];
-      a.n_img = nu * imgs_per_unit[k];
-      const int64_t tasks = ((a.n_img + a.G - 1) / a.G) * a.n_bands;
-      const int64_t blocks = std::min<int64_t>(tasks, persistent_blocks(2, stream));
-      if (blocks <= 0) continue;
-      hipLaunchKernelGGL(c.fn, dim3(unsigned(blocks)), dim3(kThreads), c.lds_bytes, stream, a);
-      HBK_LAUNCH_CHECK("conv_chain_kernel");
     }
     if (prog.gather_buf >= 0 && k_end == n_ch) {
       const int n_out = static_cast<int>(prog.gather_src.size());
       const int row = static_cast<int>(out_unit_floats / n_out);
       hipLaunchKernelGGL(embed_gather_kernel, dim3(unsigned((nu + 3) / 4)), dim3(256), 0, stream,
-                         bufs[prog.gather_buf], out + u0 * out_unit_floats, prog.d_gather, nu, prog.n_src, n_out, row);
+                         bufs[prog.gather_buf], out + u0 * out_unit_floats, d_gather, nu, prog.n_src, n_out, row);
       HBK_LAUNCH_CHECK("embed_gather_kernel");
     }
   }
   return HBK_OK;
+}
+
+// The clip / window entry points past their plan check: chains [k_begin, k_end)
+// of the clip program (or the window program) over n units in workspace chunks.
+int run_units(const hbk_embed_plan* p, bool clips, const float* in, int64_t n, int64_t in_stride, int64_t min_stride,
+              float* out, int64_t out_floats, void* workspace, int64_t workspace_bytes, void* stream, int k_begin = 0,
+              int k_end = -1) {
+  if (n < 0) return arg_error(clips ? "negative n_clips" : "negative n");
+  if (n == 0) return HBK_OK;
+  if (!in || !out || !workspace) return arg_error("NULL pointer");
+  if (in_stride < min_stride) return arg_error("mel_clip_stride < seq_frames * in_w");
+  int64_t need = 0;
+  hbk_embed_workspace_size(p, n, &need);
+  if (workspace_bytes < need) return arg_error("workspace too small");
+  return run_program(clips ? p->host.clip : p->host.win, clips ? p->clip : p->win, p->d_gather, in, n, in_stride, out,
+                     out_floats, static_cast<float*>(workspace), std::min<int64_t>(n, chunk_clips()),
+                     as_stream(stream), p->d_range, k_begin, k_end);
 }
 
 }  // namespace
@@ -3726,180 +2557,43 @@ int hbk_embed_plan_create_ex(const hbk_graph_op* ops, int32_t n_ops, int32_t in_
     hbk_embed_plan_destroy(p);
     return rc;
   };
-  p->in_h = in_h;
-  p->in_w = in_w;
-  p->split_f16 = precision == HBK_PREC_SPLIT_F16;
-  {
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&p->d_range), sizeof(int));
-    if (e == hipSuccess) e = hipMemset(p->d_range, 0, sizeof(int));
-    if (e != hipSuccess) return fail(hip_error(e, "hipMalloc range flag"));
-  }
-  for (int i = 0; i < n_win; ++i) {
-    if (win_start[i] < 0) return fail(arg_error("negative window start"));
-    p->starts.push_back(win_start[i]);
-  }
-  Dims d{in_h, in_w, 1};
-  std::vector<Dims> dims;  // per op, for one window
+  // the whole plan on the host, with every planning error, before the first device call
+  const EmbedKnobs knobs = read_embed_knobs();
+  std::vector<OpIn> graph;
   for (int i = 0; i < n_ops; ++i) {
     const hbk_graph_op& o = ops[i];
-    OpInfo op{o.kind, o.kh, o.kw, o.cin, o.cout, o.act, o.alpha, {}, {}};
-    if (o.kh <= 0 || o.kw <= 0) return fail(arg_error("kernel / pool size must be positive"));
-    if (o.kind == HBK_OP_CONV) {
-      if (o.cin != d.c || o.cout <= 0 || !o.weight || !o.bias) return fail(arg_error("bad conv op"));
-      op.w.assign(o.weight, o.weight + size_t(o.kh) * o.kw * o.cin * o.cout);
-      op.b.assign(o.bias, o.bias + o.cout);
-      if (p->split_f16)
-        for (float w : op.w)
-          if (!(std::fabs(w) < kF16Max)) {
-            set_error("hbk: op %d has a weight |w| >= 65504 (or NaN), outside the split-f16 range; "
-                      "use HBK_PREC_EXACT_F32", i);
-            return fail(HBK_ERR_UNSUPPORTED);
-          }
-      d = Dims{d.h - o.kh + 1, d.w - o.kw + 1, o.cout};
-    } else if (o.kind == HBK_OP_MAXPOOL) {
-      d = Dims{d.h / o.kh, d.w / o.kw, d.c};
-    } else {
-      return fail(arg_error("unknown op kind"));
-    }
-    if (d.h <= 0 || d.w <= 0) return fail(arg_error("graph collapses the window"));
-    p->ops.push_back(std::move(op));
-    dims.push_back(d);
+    graph.push_back(OpIn{o.kind, o.kh, o.kw, o.cin, o.cout, o.act, o.alpha, o.weight, o.bias});
   }
-  if (d.h != 1 || d.w != 1) return fail(arg_error("graph output must be 1 x 1 x C"));
-  p->out_dim = d.c;
-
-  // prefix: ops shared across the windows of a clip. A pool of height ph keeps
-  // the windows aligned iff the cumulative time stride divides every start.
-  int g = 0;
-  for (int s : p->starts) g = std::gcd(g, s);
-  // If every pool keeps the alignment, split at the last pool (any earlier
-  // split is equally valid; the tail must start with a pool).
-  int stride = 1, split = n_ops, last_pool = -1, stride_before_last = 1;
-  for (int i = 0; i < n_ops; ++i) {
-    if (p->ops[i].kind == HBK_OP_MAXPOOL) {
-      const int ns = stride * p->ops[i].kh;
-      if (g % ns != 0) {
-        split = i;
-        break;
-      }
-      last_pool = i;
-      stride_before_last = stride;
-      stride = ns;
-    }
+  int rc = plan_embed(graph, in_h, in_w, std::vector<int>(win_start, win_start + n_win),
+                      precision == HBK_PREC_SPLIT_F16, knobs, p->host);
+  if (rc) {
+    set_error("%s", p->host.error.c_str());
+    return fail(rc);
   }
-  if (split == n_ops && last_pool > 0) {
-    split = last_pool;
-    stride = stride_before_last;
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&p->d_range), sizeof(int));
+  if (e == hipSuccess) e = hipMemset(p->d_range, 0, sizeof(int));
+  if (e != hipSuccess) return fail(hip_error(e, "hipMalloc range flag"));
+  rc = realise_program(p->host.clip, knobs.debug, p->clip);
+  if (rc) return fail(rc);
+  if (const std::vector<int>& map = p->host.clip.gather_src; !map.empty()) {
+    e = hipMalloc(reinterpret_cast<void**>(&p->d_gather), map.size() * sizeof(int));
+    if (e == hipSuccess) e = hipMemcpy(p->d_gather, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail(hip_error(e, "embed gather map"));
+    if (knobs.debug) fputs(p->host.dedup_debug.c_str(), stderr);
   }
-  // the tail must start with a pool (its input pool) and contain a conv
-  if (split == n_ops || split == 0) {
-    set_error("hbk: graph has no window-splitting pool; use hbk_embed_windows");
-    return fail(HBK_ERR_UNSUPPORTED);
-  }
-  p->n_prefix = split;
-  p->split_stride = stride;
-  const int max_start = *std::max_element(p->starts.begin(), p->starts.end());
-  p->seq_frames = max_start + in_h;
-
-  int rc;
-  // ---- clip program: prefix over [seq_frames, in_w, 1] per clip ----
-  {
-    std::vector<Dims> od;
-    rc = build_segment(p->ops, 0, split, Dims{p->seq_frames, in_w, 1}, 1, {0}, 0, in_w, -1,
-                       p->split_f16, p->clip_prog, &od);
-    if (rc) return fail(rc);
-    const Dims pre = od.back();
-    // window rows at the split, for one window
-    const Dims wd = dims[split - 1];
-    std::vector<int> roff;
-    for (int s : p->starts) roff.push_back(s / stride);
-    for (int r : roff)
-      if (r + wd.h > pre.h) return fail(arg_error("window start beyond the frame sequence"));
-    const size_t n_pre = p->clip_prog.chains.size();
-    // Phase deduplication of the tail: with S = the tail's cumulative pool
-    // stride, windows whose prefix-row offsets are congruent mod S see the same
-    // pool grid, and the tail's valid convs are translation-equivariant, so
-    // ONE "phase image" per residue (rows [phi, phi + H)) yields every such
-    // window as output row (r - phi) / S. Used when the phase images' output
-    // fits the per-clip output (n_phase x rows <= n_win) and HBK_EMBED_NO_DEDUP
-    // is unset; the output rows are gathered into window order afterwards.
-    std::vector<int> phases, win_src;
-    int H = 0;
-    {
-      int S = 1;
-      for (int i = split; i < n_ops; ++i)
-        if (p->ops[i].kind == HBK_OP_MAXPOOL) S *= p->ops[i].kh;
-      for (int r : roff)
-        if (std::find(phases.begin(), phases.end(), r % S) == phases.end()) phases.push_back(r % S);
-      std::sort(phases.begin(), phases.end());
-      for (int r : roff) H = std::max(H, r - r % S + wd.h);
-      bool ok = S > 1 && !getenv("HBK_EMBED_NO_DEDUP") && int(phases.size()) < n_win;
-      for (int ph : phases) ok = ok && ph + H <= pre.h;
-      // tail output rows for an H-row phase image
-      Dims t{H, wd.w, wd.c};
-      for (int i = split; i < n_ops && ok; ++i) {
-        const OpInfo& o = p->ops[i];
-        t = o.kind == HBK_OP_CONV ? Dims{t.h - o.kh + 1, t.w - o.kw + 1, o.cout} : Dims{t.h / o.kh, t.w / o.kw, t.c};
-        ok = t.h > 0 && t.w > 0;
-      }
-      ok = ok && t.w == 1 && int(phases.size()) * t.h <= n_win;
-      if (ok) {
-        for (int r : roff) {
-          const int ph = int(std::find(phases.begin(), phases.end(), r % S) - phases.begin());
-          const int row = (r - r % S) / S;
-          ok = ok && row < t.h;
-          win_src.push_back(ph * t.h + row);
-        }
-        p->clip_prog.n_src = int(phases.size()) * t.h;
-      }
-      if (!ok) phases.clear();
-    }
-    if (!phases.empty()) {
-      p->clip_prog.gather_src = win_src;
-      hipError_t e = hipMalloc(reinterpret_cast<void**>(&p->clip_prog.d_gather), win_src.size() * sizeof(int));
-      if (e == hipSuccess)
-        e = hipMemcpy(p->clip_prog.d_gather, win_src.data(), win_src.size() * sizeof(int), hipMemcpyHostToDevice);
-      if (e != hipSuccess) return fail(hip_error(e, "embed gather map"));
-      rc = build_segment(p->ops, split, n_ops, Dims{H, wd.w, wd.c}, int(phases.size()), phases,
-                         int64_t(pre.h) * pre.w * pre.c, pre.w * pre.c, 0, p->split_f16, p->clip_prog, nullptr);
-      if (getenv("HBK_DEBUG_EMBED"))
-        fprintf(stderr, "hbk tail dedup: %zu phase images of %d rows per clip for %d windows\n", phases.size(), H,
-                n_win);
-    } else {
-      rc = build_segment(p->ops, split, n_ops, Dims{wd.h, wd.w, wd.c}, n_win, roff,
-                         int64_t(pre.h) * pre.w * pre.c, pre.w * pre.c, 0, p->split_f16, p->clip_prog,
-                         nullptr);
-    }
-    if (rc) return fail(rc);
-    for (size_t k = 0; k < p->clip_prog.chains.size(); ++k) {
-      if (k < n_pre) p->prefix_macs += p->clip_prog.chains[k].macs_per_img;
-      else p->tail_macs += p->clip_prog.chains[k].macs_per_img;
-    }
-    // tail_macs is reported per window: with phase images, their MACs per clip / n_win
-    if (!phases.empty()) p->tail_macs *= double(phases.size()) / double(n_win);
-    assign_buffers(p->clip_prog, 1);
-  }
-  // ---- window program: every op per window ----
-  {
-    std::vector<Dims> od;
-    rc = build_segment(p->ops, 0, n_ops, Dims{in_h, in_w, 1}, 1, {0}, int64_t(in_h) * in_w, in_w,
-                       -1, p->split_f16, p->win_prog, &od);
-    if (rc) return fail(rc);
-    assign_buffers(p->win_prog, 1);
-  }
+  rc = realise_program(p->host.win, knobs.debug, p->win);
+  if (rc) return fail(rc);
   *plan = p;
   return HBK_OK;
 }
 
 int hbk_embed_plan_destroy(hbk_embed_plan* p) {
   if (!p) return HBK_OK;
-  for (auto* prog : {&p->clip_prog, &p->win_prog}) {
-    for (auto& c : prog->chains) {
-      (void)hipFree(c.d_blob);
-      if (c.d_p0) (void)hipFree(c.d_p0);
-    }
-    if (prog->d_gather) (void)hipFree(prog->d_gather);
-  }
+  for (auto* dev : {&p->clip, &p->win})
+    for (auto& c : *dev)
+      for (hbk::Slot* s : {&c.pattern, &c.base})
+        if (s->d_blob) (void)hipFree(s->d_blob);
+  if (p->d_gather) (void)hipFree(p->d_gather);
   if (p->d_range) (void)hipFree(p->d_range);
   delete p;
   return HBK_OK;
@@ -3909,42 +2603,18 @@ int hbk_embed_plan_info(const hbk_embed_plan* p, int32_t* out_dim, int32_t* n_pr
                         int32_t* n_chains, double* prefix_macs, double* tail_macs,
                         int32_t* seq_frames) {
   if (!p) return hbk::arg_error("plan is NULL");
-  if (out_dim) *out_dim = p->out_dim;
-  if (n_prefix_ops) *n_prefix_ops = p->n_prefix;
-  if (n_chains) *n_chains = static_cast<int32_t>(p->clip_prog.chains.size());
-  if (prefix_macs) *prefix_macs = p->prefix_macs;
-  if (tail_macs) *tail_macs = p->tail_macs;
-  if (seq_frames) *seq_frames = p->seq_frames;
+  if (out_dim) *out_dim = p->host.out_dim;
+  if (n_prefix_ops) *n_prefix_ops = p->host.n_prefix;
+  if (n_chains) *n_chains = static_cast<int32_t>(p->host.clip.chains.size());
+  if (prefix_macs) *prefix_macs = p->host.prefix_macs;
+  if (tail_macs) *tail_macs = p->host.tail_macs;
+  if (seq_frames) *seq_frames = p->host.seq_frames;
   return HBK_OK;
 }
 
 }  // extern "C"
 
 namespace hbk {
-namespace {
-
-// Per-unit (clip or window) workspace floats of each ping-pong buffer and the
-// images per unit of each chain.
-void program_geometry(const Program& prog, bool clip_path, int n_win, std::vector<int64_t>& imgs,
-                      std::vector<int64_t>& bufs) {
-  imgs.clear();
-  bufs.assign(2, 0);
-  bool tail = false;
-  int tail_imgs = n_win;
-  for (size_t k = 0; k < prog.chains.size(); ++k) {
-    const ChainPlan& c = prog.chains[k];
-    const int ipc = c.split ? c.x.ipc : c.args.ipc;
-    const int64_t ois = c.split ? c.x.out_img_stride : c.args.out_img_stride;
-    if (clip_path && ipc > 1 && !tail) {
-      tail = true;
-      tail_imgs = ipc;  // n_win, or the phase images of a deduplicated tail
-    }
-    imgs.push_back(tail ? tail_imgs : 1);
-    if (c.dst_buf >= 0) bufs[c.dst_buf] = std::max(bufs[c.dst_buf], ois * imgs.back());
-  }
-}
-
-}  // namespace
 
 // ---- NaN rows (embeddings.py:209-234): in place, no host synchronisation ----
 // Three grid-wide launches, each a no-op past one load when the batch has no NaN row:
@@ -4060,13 +2730,8 @@ int hbk_embed_workspace_size(const hbk_embed_plan* p, int64_t n, int64_t* bytes)
   if (!p || !bytes) return arg_error("plan/bytes is NULL");
   if (n < 0) return arg_error("negative n");
   const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n, chunk_clips()));
-  std::vector<int64_t> imgs, bc, bw;
-  program_geometry(p->clip_prog, true, int(p->starts.size()), imgs, bc);
-  const int64_t chunk_w = std::max<int64_t>(1, std::min<int64_t>(n, chunk_clips()));
-  program_geometry(p->win_prog, false, 1, imgs, bw);
-  const int64_t fc = chunk * (bc[0] + bc[1]);
-  const int64_t fw = chunk_w * (bw[0] + bw[1]);
-  *bytes = std::max(fc, fw) * int64_t(sizeof(float)) + 256;
+  const int64_t *bc = p->host.clip.buf_floats, *bw = p->host.win.buf_floats;
+  *bytes = chunk * std::max(bc[0] + bc[1], bw[0] + bw[1]) * int64_t(sizeof(float)) + 256;
   return HBK_OK;
 }
 
@@ -4074,30 +2739,17 @@ int hbk_embed_clips(const hbk_embed_plan* p, const float* mel, int64_t n_clips, 
                     float* out, void* workspace, int64_t workspace_bytes, void* stream) {
   using namespace hbk;
   if (!p) return arg_error("plan is NULL");
-  if (n_clips < 0) return arg_error("negative n_clips");
-  if (n_clips == 0) return HBK_OK;
-  if (!mel || !out || !workspace) return arg_error("NULL pointer");
-  if (mel_clip_stride < int64_t(p->seq_frames) * p->in_w) return arg_error("mel_clip_stride < seq_frames * in_w");
-  int64_t need = 0;
-  hbk_embed_workspace_size(p, n_clips, &need);
-  if (workspace_bytes < need) return arg_error("workspace too small");
-  std::vector<int64_t> imgs, bufs;
-  program_geometry(p->clip_prog, true, int(p->starts.size()), imgs, bufs);
-  const int64_t chunk = std::min<int64_t>(n_clips, chunk_clips());
-  return run_program(p->clip_prog, mel, n_clips, mel_clip_stride, out,
-                     int64_t(p->starts.size()) * p->out_dim, static_cast<float*>(workspace), chunk,
-                     as_stream(stream), imgs, bufs, p->d_range);
+  return run_units(p, true, mel, n_clips, mel_clip_stride, int64_t(p->host.seq_frames) * p->host.in_w, out,
+                   int64_t(p->host.n_win) * p->host.out_dim, workspace, workspace_bytes, stream);
 }
 
 int hbk_embed_split_info(const hbk_embed_plan* p, int32_t n_front, int64_t* mid_floats_per_clip) {
   using namespace hbk;
   if (!p || !mid_floats_per_clip) return arg_error("plan/mid_floats_per_clip is NULL");
-  const int n = static_cast<int>(p->clip_prog.chains.size());
+  const int n = static_cast<int>(p->host.clip.chains.size());
   if (n_front < 1 || n_front >= n) return arg_error("n_front must be in [1, n_chains - 1]");
-  std::vector<int64_t> imgs, bufs;
-  program_geometry(p->clip_prog, true, int(p->starts.size()), imgs, bufs);
-  const ChainPlan& c = p->clip_prog.chains[n_front - 1];
-  *mid_floats_per_clip = (c.split ? c.x.out_img_stride : c.args.out_img_stride) * imgs[n_front - 1];
+  const ChainHost& c = p->host.clip.chains[n_front - 1];
+  *mid_floats_per_clip = c.out_img_stride * c.imgs_per_unit;
   return HBK_OK;
 }
 
@@ -4107,18 +2759,8 @@ int hbk_embed_clips_front(const hbk_embed_plan* p, const float* mel, int64_t n_c
   int64_t mid_floats = 0;
   int rc = hbk_embed_split_info(p, n_front, &mid_floats);
   if (rc) return rc;
-  if (n_clips < 0) return arg_error("negative n_clips");
-  if (n_clips == 0) return HBK_OK;
-  if (!mel || !mid || !workspace) return arg_error("NULL pointer");
-  if (mel_clip_stride < int64_t(p->seq_frames) * p->in_w) return arg_error("mel_clip_stride < seq_frames * in_w");
-  int64_t need = 0;
-  hbk_embed_workspace_size(p, n_clips, &need);
-  if (workspace_bytes < need) return arg_error("workspace too small");
-  std::vector<int64_t> imgs, bufs;
-  program_geometry(p->clip_prog, true, int(p->starts.size()), imgs, bufs);
-  const int64_t chunk = std::min<int64_t>(n_clips, chunk_clips());
-  return run_program(p->clip_prog, mel, n_clips, mel_clip_stride, mid, mid_floats, static_cast<float*>(workspace),
-                     chunk, as_stream(stream), imgs, bufs, p->d_range, 0, n_front);
+  return run_units(p, true, mel, n_clips, mel_clip_stride, int64_t(p->host.seq_frames) * p->host.in_w, mid,
+                   mid_floats, workspace, workspace_bytes, stream, 0, n_front);
 }
 
 int hbk_embed_clips_back(const hbk_embed_plan* p, const float* mid, int64_t n_clips, int32_t n_front, float* out,
@@ -4127,34 +2769,16 @@ int hbk_embed_clips_back(const hbk_embed_plan* p, const float* mid, int64_t n_cl
   int64_t mid_floats = 0;
   int rc = hbk_embed_split_info(p, n_front, &mid_floats);
   if (rc) return rc;
-  if (n_clips < 0) return arg_error("negative n_clips");
-  if (n_clips == 0) return HBK_OK;
-  if (!mid || !out || !workspace) return arg_error("NULL pointer");
-  int64_t need = 0;
-  hbk_embed_workspace_size(p, n_clips, &need);
-  if (workspace_bytes < need) return arg_error("workspace too small");
-  std::vector<int64_t> imgs, bufs;
-  program_geometry(p->clip_prog, true, int(p->starts.size()), imgs, bufs);
-  const int64_t chunk = std::min<int64_t>(n_clips, chunk_clips());
-  return run_program(p->clip_prog, mid, n_clips, mid_floats, out, int64_t(p->starts.size()) * p->out_dim,
-                     static_cast<float*>(workspace), chunk, as_stream(stream), imgs, bufs, p->d_range, n_front, -1);
+  return run_units(p, true, mid, n_clips, mid_floats, 0, out, int64_t(p->host.n_win) * p->host.out_dim, workspace,
+                   workspace_bytes, stream, n_front, -1);
 }
 
 int hbk_embed_windows(const hbk_embed_plan* p, const float* windows, int64_t n, float* out,
                       void* workspace, int64_t workspace_bytes, void* stream) {
   using namespace hbk;
   if (!p) return arg_error("plan is NULL");
-  if (n < 0) return arg_error("negative n");
-  if (n == 0) return HBK_OK;
-  if (!windows || !out || !workspace) return arg_error("NULL pointer");
-  int64_t need = 0;
-  hbk_embed_workspace_size(p, n, &need);
-  if (workspace_bytes < need) return arg_error("workspace too small");
-  std::vector<int64_t> imgs, bufs;
-  program_geometry(p->win_prog, false, 1, imgs, bufs);
-  const int64_t chunk = std::min<int64_t>(n, chunk_clips());
-  return run_program(p->win_prog, windows, n, int64_t(p->in_h) * p->in_w, out, p->out_dim,
-                     static_cast<float*>(workspace), chunk, as_stream(stream), imgs, bufs, p->d_range);
+  return run_units(p, false, windows, n, int64_t(p->host.in_h) * p->host.in_w, 0, out, p->host.out_dim, workspace,
+                   workspace_bytes, stream);
 }
 
 int64_t hbk_nan_rows_workspace_size(int64_t n) {

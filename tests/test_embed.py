@@ -166,6 +166,35 @@ def test_embed_pattern_kernels_match_generic_path(monkeypatch, capfd):
         assert np.abs(outs["p0s"] - outs[name]).max() <= 1e-5 * (1.0 + np.abs(ref).max()), name
 
 
+@pytest.mark.gpu
+def test_embed_pattern_falls_through_to_generic_kernel_on_odd_clip_stride(monkeypatch):
+    """A mel tensor whose clip stride (136 * 32 + 1 floats) is no multiple of 4:
+    chain 0's pattern kernel fails the stride test at launch and the chain runs on
+    the generic split-f16 kernel with scalar staging, while chains 1-3 (workspace
+    buffers) stay on their pattern kernels. The result meets the oracle, is
+    within the cross-path bound of the contiguous result, and equals bit for bit
+    that of a plan whose chain 0 has no pattern kernel (HBK_EMBED_NO_P0)."""
+    from heybuddy.embedding_graph import se20_graph
+    from heybuddy.kernels import EmbedPlan
+    g = se20_graph()
+    mel = _mel_clips(3, seed=17)[:, :136]
+    ref = _oracle_clip_embeddings(g, mel)
+    stride = 136 * 32 + 1
+    flat = torch.zeros(3 * stride + 3, device="cuda")
+    assert flat.data_ptr() % 16 == 0
+    odd = torch.as_strided(flat, (3, 136, 32), (stride, 32, 1))
+    odd.copy_(torch.from_numpy(mel))
+    plan = EmbedPlan(g, precision="split")
+    out = plan.clips(odd).cpu().numpy()
+    same = plan.clips(odd.contiguous()).cpu().numpy()
+    monkeypatch.setenv("HBK_EMBED_NO_P0", "1")
+    no_p0 = EmbedPlan(g, precision="split").clips(odd.contiguous()).cpu().numpy()
+    ok, worst = _close(out, ref)
+    assert out.shape == (3, 16, 96) and ok, f"max |diff| {worst}"
+    assert np.abs(out - same).max() <= 1e-5 * (1.0 + np.abs(ref).max())
+    np.testing.assert_array_equal(out, no_p0)
+
+
 def _generic_graph(seed=9):
     """Shapes the SE20 stand-in does not have: cin 1 with a 2x3 kernel, channel
     counts that are not multiples of 8 / 32 (12, 40, 70, 33), a 1x1 conv, a
