@@ -574,7 +574,7 @@ __device__ __forceinline__ void split8m(const float (&v)[8], h8m& hi, h8m& lo) {
     lo[e + 1] = l[1];
   }
 }
-// reduce-scatter across lane ^ 16 / lane ^ 32 (v_permlane*_swap; see hbk_augment.hip's pv_swap_add)
+// reduce-scatter across lane ^ 16 / lane ^ 32 (v_permlane*_swap; see hbk_pitch.hip's pv_swap_add, the same function)
 template <bool kSwap16>
 __device__ __forceinline__ float mel_swap_add(float x, float y) {
   if (kSwap16)

@@ -935,6 +935,7 @@ def _tanh_distortion_op(x: torch.Tensor, amount: torch.Tensor, rows: torch.Tenso
 
 
 BAND_STOP_CIRCULAR_MAX_HALF = 512  # HBK_BAND_STOP_CIRCULAR_MAX_HALF (include/hbk.h)
+BAND_STOP_PARTITION_TAPS = 11521  # HBK_BAND_STOP_PARTITION_TAPS (include/hbk.h): taps per overlap-save partition
 
 
 class ReverbPlan:
@@ -1151,7 +1152,8 @@ class ReverbPlan:
         pairs, filt = np.unique(np.stack([lo_h.numpy(), hi_h.numpy()], 1), axis=0, return_inverse=True)
         # julius LowPassFilters.half_size = int(zeros / min(cutoffs) / 2), zeros = 8
         half = np.array([int(8 / float(c) / 2) for c in pairs[:, 0].tolist()], dtype=np.int32)
-        nspec = np.where(half <= BAND_STOP_CIRCULAR_MAX_HALF, 1, (2 * half + 1 + 11520) // 11521).astype(np.int32)
+        nspec = np.where(half <= BAND_STOP_CIRCULAR_MAX_HALF, 1,
+                         (2 * half + BAND_STOP_PARTITION_TAPS) // BAND_STOP_PARTITION_TAPS).astype(np.int32)
         spec0 = np.concatenate([[0], np.cumsum(nspec)[:-1]]).astype(np.int32)
         s_filt = np.repeat(np.arange(len(pairs), dtype=np.int32), nspec)
         s_part = np.concatenate([[-1] if h <= BAND_STOP_CIRCULAR_MAX_HALF else np.arange(k)

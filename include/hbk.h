@@ -488,14 +488,15 @@ int hbk_augment_colored(const hbk_reverb_plan* plan, const float* x, int64_t n_c
  * f_half[f] = int(8 / f_lo / 2); its spectra are slots f_spec0[f] .. of the
  * n_spectra listed in s_filt / s_part: ONE slot with s_part = -1 when
  * f_half <= HBK_BAND_STOP_CIRCULAR_MAX_HALF (circular convolution + direct edge
- * correction), else ceil((2 f_half + 1) / 11521) slots with s_part = 0, 1, ..
- * (overlap-save partitions). For entry e < n, clip row r = idx[e] of x
+ * correction), else ceil((2 f_half + 1) / HBK_BAND_STOP_PARTITION_TAPS) slots
+ * with s_part = 0, 1, .. (overlap-save partitions). For entry e < n, clip row r = idx[e] of x
  * [*, x_stride] (first T = 23040 samples):
  *   out[r] = x[r] - julius.bandpass_filter(x[r], f_lo[filt[e]], f_hi[filt[e]])
  * (windowed-sinc lowpasses over the replicate-padded clip). Rows not listed are
  * not touched; out may equal x. workspace: hbk_band_stop_workspace_size bytes.
  * Device pointers. */
 #define HBK_BAND_STOP_CIRCULAR_MAX_HALF 512
+#define HBK_BAND_STOP_PARTITION_TAPS 11521 /* T - T / 2 + 1: the taps of one overlap-save partition */
 int64_t hbk_band_stop_workspace_size(int64_t n, int32_t n_filters, int32_t n_spectra, void* stream);
 int hbk_band_stop(const hbk_reverb_plan* plan, const float* x, int64_t x_stride, int64_t n, const int32_t* idx,
                   const int32_t* filt, int32_t n_filters, const float* f_lo, const float* f_hi,

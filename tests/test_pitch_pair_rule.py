@@ -1,5 +1,5 @@
 """The rule hbk_pitch_shift pairs a call's clips by (ps_span_kernel / ps_rank_kernel
-/ ps_group_kernel in csrc/hbk_augment.hip), written in numpy and run on the
+/ ps_group_kernel in csrc/hbk_pitch.hip), written in numpy and run on the
 training clips' own spans.
 
 A vocoder workgroup runs the union of its two clips' non-silent spans plus 36

@@ -139,8 +139,9 @@ def test_span_path_matches_oracle(shift, clips, oracle, device):
 
 
 def test_span_path_against_full_path(clips, tmp_path):
-    """HBK_PS_SPAN=0 against the default, each in a fresh process (the switch
-    is read once): bit-identical before (the clip's last non-zero input sample
+    """HBK_PS_SPAN=0 against the default, each in a fresh process (which sees
+    only its own environment; the switch is read on every call, see
+    test_span_switch_is_read_per_call): bit-identical before (the clip's last non-zero input sample
     - 256), |a - b| <= 1e-3 of the clip's peak everywhere else."""
     me = os.path.abspath(__file__)
     env = {k: v for k, v in os.environ.items() if k != "HBK_PS_SPAN"}
@@ -168,6 +169,49 @@ def test_span_path_against_full_path(clips, tmp_path):
             print(f"shift {num}/{den} clip {p}: bits equal before {cut}: {same}; max |a - b| {d:.2e}, peak {peak:.2e}")
             assert same, f"shift {num}/{den} clip {p}: the span path differs from the full path before sample {cut}"
             assert d <= 1e-3 * peak, f"shift {num}/{den} clip {p}: |a - b| {d:.2e} > 1e-3 of peak {peak:.2e}"
+
+
+def test_span_switch_is_read_per_call(clips):
+    """HBK_PS_SPAN toggled between calls of ONE process: five clips (a silent one,
+    a full-length one, three placed bursts; the odd count leaves one vocoder
+    workgroup with a lone clip), both shifts. The HBK_PS_SPAN=0 call against the
+    default call holds what test_span_path_against_full_path accepts across two
+    processes; the HBK_PS_SPAN=1 call equals the default call bit for bit."""
+    import torch
+    from heybuddy.kernels import pitch_shift
+    rows = ROWS[[6, 11, 0, 2, 9]]  # silent, full length, bursts at 9,000, at the end, at 18,000
+    x = np.ascontiguousarray(clips[rows])
+    idx = torch.arange(len(rows), dtype=torch.int32)
+
+    def run(num, den, span):
+        if span is None:
+            os.environ.pop("HBK_PS_SPAN", None)
+        else:
+            os.environ["HBK_PS_SPAN"] = span
+        xd = torch.from_numpy(x).cuda()
+        return pitch_shift(xd, idx, num, den, out=xd).cpu()
+
+    before = os.environ.get("HBK_PS_SPAN")
+    try:
+        for num, den in SHIFTS:
+            default, full, on = run(num, den, None), run(num, den, "0"), run(num, den, "1")
+            assert torch.equal(on, default), f"shift {num}/{den}: HBK_PS_SPAN=1 differs from the default call"
+            a, b = default.numpy(), full.numpy()
+            assert not a[0].any() and not b[0].any()
+            for p in range(len(rows)):
+                nz = np.flatnonzero(x[p])
+                cut = max(int(nz[-1]) - 256, 0) if nz.size else 0
+                same = np.array_equal(a[p, :cut].view(np.int32), b[p, :cut].view(np.int32))
+                peak = max(float(np.abs(a[p]).max()), float(np.abs(b[p]).max()))
+                d = float(np.abs(a[p].astype(np.float64) - b[p]).max())
+                print(f"shift {num}/{den} clip {p}: bits equal before {cut}: {same}; max |a - b| {d:.2e}, peak {peak:.2e}")
+                assert same, f"shift {num}/{den} clip {p}: the span call differs from the full call before sample {cut}"
+                assert d <= 1e-3 * peak, f"shift {num}/{den} clip {p}: |a - b| {d:.2e} > 1e-3 of peak {peak:.2e}"
+    finally:
+        if before is None:
+            os.environ.pop("HBK_PS_SPAN", None)
+        else:
+            os.environ["HBK_PS_SPAN"] = before
 
 
 @pytest.mark.parametrize("shift", SHIFTS, ids=lambda s: f"{s[0]}_{s[1]}")

@@ -10,7 +10,8 @@ call starts from the same input (the shift runs on a fresh copy).
 
 --alternate runs both cases in fresh child processes, ROUNDS times in turn:
 [the library --parent-lib names,] the default library, and the default library
-with HBK_PS_SPAN=0 (the switch is read once per process)."""
+with HBK_PS_SPAN=0 (the switch is read on every call; a fresh process per
+case keeps the timings independent of one another)."""
 import os
 import subprocess
 import sys
