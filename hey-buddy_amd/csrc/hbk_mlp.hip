@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "hbk_common.h"
+#include "hbk_mlp_gate.h"
 #include "hbk_mlp_internal.h"
 
 namespace hbk {
@@ -305,25 +306,13 @@ __global__ void gate_kernel(const float* __restrict__ stats, float* __restrict__
                             float* __restrict__ hist, int hist_cap, float beta1, float beta2) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   const float n_sel = stats[0];
-  float acc_samples = state[0], acc_steps = state[1], t = state[2];
   const int step = static_cast<int>(state[3]);
-  float fire = 0.f, scale = 0.f, loss = 0.f;
-  const float used_steps = acc_steps;
-  if (n_sel > 0.f) {
-    loss = stats[1] / n_sel / acc_steps;
-    acc_samples += n_sel;
-    if (acc_samples < 128.f) {
-      acc_steps += 1.f;
-    } else {
-      fire = 1.f;
-      scale = 1.f / (n_sel * acc_steps);
-      acc_steps = 1.f;
-      acc_samples = 0.f;
-      t += 1.f;
-    }
-  }
-  state[0] = acc_samples;
-  state[1] = acc_steps;
+  const float used_steps = state[1];
+  const float loss = n_sel > 0.f ? stats[1] / n_sel / used_steps : 0.f;
+  const StepGate g = step_gate(state[0], used_steps, state[2], n_sel);
+  const float fire = g.fire, scale = g.scale, t = g.adam_t;
+  state[0] = g.acc_samples;
+  state[1] = g.acc_steps;
   state[2] = t;
   state[3] = static_cast<float>(step + 1);
   ctrl[0] = fire;
@@ -703,8 +692,11 @@ int hbk_mlp_step_fwd_bwd(const hbk_mlp_plan* p, const float* params, const float
   if (ws_bytes < mlp_fused_ws_floats(*p, batch) * int64_t(sizeof(float))) return arg_error("workspace too small");
   if (n32 < 0 || n16 < 0) return arg_error("negative pool size");
   if (!idx && n32 < batch) return arg_error("idx NULL: pool32 must hold the batch rows");
-  if (flags & ~(HBK_STEP_XHAT_READY | HBK_STEP_PREFETCH_NEXT | HBK_STEP_WEIGHTS_READY | HBK_STEP_DEFER_PARTIALS))
+  if (flags & ~(HBK_STEP_XHAT_READY | HBK_STEP_PREFETCH_NEXT | HBK_STEP_WEIGHTS_READY | HBK_STEP_DEFER_PARTIALS |
+                HBK_STEP_GATE_SKIP))
     return arg_error("unknown flags");
+  if ((flags & HBK_STEP_GATE_SKIP) && !(flags & HBK_STEP_DEFER_PARTIALS))
+    return arg_error("HBK_STEP_GATE_SKIP needs HBK_STEP_DEFER_PARTIALS (the update that follows must own the slabs)");
   if (!pool32 && !pool16) return arg_error("no embedding pool");
   return mlp_fused_run(*p, params, pool32, n32, pool16, n16, idx, idx_step_stride, idx_steps, y, y_step_stride,
                        static_cast<int>(batch), state, parity, sched,

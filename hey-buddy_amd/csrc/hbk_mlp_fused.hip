@@ -43,6 +43,12 @@
 //   k4_update  the < 128-sample accumulation gate, Adam, zeroing of the bucket for
 //              the next step, and the weight cache (k0_wsplit writes it when the
 //              previous step's k4 did not)
+//   HBK_STEP_GATE_SKIP (with the deferred slabs: train_indexed in one process): a
+//              step whose update will not fire drops its gradient, as the reference
+//              never calls backward() there (trainer.py:443-465). n_sel is final
+//              once k2 has run, so k3 / k3s decide the gate themselves (step_gate,
+//              hbk_mlp_gate.h: k4's rule on k4's words) and leave before any work,
+//              and k4 decides first and then only zeroes what k2 added to the bucket
 //
 // Where the rest lives: hbk_mlp_plan.h, the step's planning as pure host C++ (the
 // variant, every kernel's geometry, the job tables' shapes, the workspace layout,
@@ -73,6 +79,7 @@
 
 #include "hbk_common.h"
 #include "hbk_mlp_dev.h"
+#include "hbk_mlp_gate.h"
 #include "hbk_mlp_internal.h"
 #include "hbk_mlp_plan.h"
 
@@ -156,6 +163,33 @@ __device__ __forceinline__ T* bck_(T* p, int nbytes, int line) {
 
 __device__ __forceinline__ int step_of(const float* state, int parity) {
   return state ? static_cast<int>(state[parity * 8 + 3]) : 0;
+}
+
+// HBK_STEP_GATE_SKIP: the words the step's accumulation gate is decided from, for the kernels
+// that run once they are final (after k2: the weight gradients, then k4). st: the step's
+// read-only state half, stats: the bucket's statistics (n_sel is statistic 0); NULL st: no
+// skip, the kernel does all its work. A kernel loads the two words first (scalar loads,
+// issued with its prologue's own loads, not in front of them) and asks gate_drops() where
+// it needs the answer: true = the update that follows will not fire, so the step's gradient
+// is dropped (zero_grad every step, trainer.py:404) and nothing that only feeds it is needed.
+// The decision is step_gate's, on the same words k4 reads: the kernels cannot disagree.
+struct GateWords {
+  const float* st;
+  const float* stats;
+};
+struct GateSeen {
+  float acc_samples, n_sel;
+};
+__device__ __forceinline__ GateSeen gate_load(const GateWords& g) {
+  GateSeen s{0.f, kGateSamples};  // (no skip: a step that fires)
+  if (g.st) {
+    s.acc_samples = *BCK(&g.st[0], 4);
+    s.n_sel = *BCK(&g.stats[0], 4);
+  }
+  return s;
+}
+__device__ __forceinline__ bool gate_drops(const GateSeen& s) {
+  return step_gate(s.acc_samples, 1.f, 0.f, s.n_sel).fire == 0.f;
 }
 
 // ------------------------------------------------------------------ k1 ----
@@ -1279,13 +1313,16 @@ struct K3Args {
   int64_t g_off, b_off;  // norm_in gamma / beta in the parameter layout
   float* part;           // [KS][pstride] partial slabs
   int64_t pstride;
+  GateWords gate;        // HBK_STEP_GATE_SKIP (st NULL: off)
 };
 
 // STEPS: batch rows per split / 32 (the grid's split count follows); the launch
 // takes kK3Steps on a wide stream and kK3StepsNarrow on a CU-masked one of at
 // most kK3NarrowCUs CUs (fewer, longer workgroups: see kK3Steps' sweep)
+// (the narrow form is held at its 4 waves per SIMD, <= 128 registers: the gate's early
+// exit moved the allocation from 122 to 130 without the bound)
 template <int STEPS, int G>
-__global__ void __launch_bounds__(256) k3_wgrad_kernel(K3Args a) {
+__global__ void __launch_bounds__(256, STEPS <= 4 && G == 1 ? 4 : 1) k3_wgrad_kernel(K3Args a) {
   constexpr int kK3Steps = STEPS, kK3Rows = 32 * STEPS, kYLdH = kK3Rows + 8;
   __shared__ __attribute__((aligned(16))) _Float16 yh[kTN * kYLdH];
   __shared__ __attribute__((aligned(16))) _Float16 yl[kTN * kYLdH];
@@ -1337,6 +1374,9 @@ __global__ void __launch_bounds__(256) k3_wgrad_kernel(K3Args a) {
   load_y(rbase);
 #pragma unroll
   for (int u = 0; u < kK3Steps; ++u) load_x(rbase, u);
+  // HBK_STEP_GATE_SKIP: two scalar words, in flight with the tile's loads above. (Uniform) the
+  // update will not fire: no slab is stored, the previous step's stay, k4 reads none
+  if (gate_drops(gate_load(a.gate))) return;
   const f4 z = {0.f, 0.f, 0.f, 0.f};
   f4 ssum[2] = {z, z};
   f4 acc[2][2] = {{z, z}, {z, z}};
@@ -1549,6 +1589,7 @@ struct K3sArgs {
   float* part;  // [S][pstride]
   int64_t pstride;
   int sparse;  // 1: walk the live row tiles only (0: every tile; HBK_STEP_DENSE=1, or n_rt > kK3sMaxTiles)
+  GateWords gate;  // HBK_STEP_GATE_SKIP (st NULL: off)
 };
 // XOR swizzle of the 16-B chunks of a 256-B row (the input layer's [32][128] half images):
 // conflict-free ds_write_b128 of whole chunks and ds_read_b64_tr_b16 of the B operand
@@ -1969,15 +2010,21 @@ __global__ void __launch_bounds__(kK3sThr, kOcc) k3s_kernel(K3sArgs a) {
   // the same list everywhere, no atomics), and the job's S splits share the list's 32-row steps
   // evenly, q = ceil(steps / S) each, so the sums keep the ascending row order. A split past
   // the list writes its slab(s) as zeros: k4 and k3_fold go on summing all S slabs.
+  // HBK_STEP_GATE_SKIP: the gate's two words are loaded with the tile maxima (one latency for
+  // both), and a step whose update will not fire ends here, uniformly in every workgroup:
+  // before the list, any pool or activation load and any slab store. The slabs keep what an
+  // earlier step left; k4 decides by the same rule and reads none of them.
   int n_live = a.n_rt, q = jb.R / 32;
+  const GateSeen gate = gate_load(a.gate);
+  f4 mx = {0.f, 0.f, 0.f, 0.f};
+  if (a.sparse && static_cast<int>(threadIdx.x) < a.n_rt) {
+    static_assert(kK2Waves == 4, "a tile's maxima are one float4");
+    mx = *BCK(reinterpret_cast<const f4*>(a.maxS + (static_cast<int64_t>(a.n_jobs - 1) * a.n_rt + threadIdx.x) * kK2Waves), 16);
+  }
+  if (gate_drops(gate)) return;
   if (a.sparse) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    bool lv = false;
-    if (tid < a.n_rt) {
-      static_assert(kK2Waves == 4, "a tile's maxima are one float4");
-      const f4 v = *BCK(reinterpret_cast<const f4*>(a.maxS + (static_cast<int64_t>(a.n_jobs - 1) * a.n_rt + tid) * kK2Waves), 16);
-      lv = v[0] != 0.f || v[1] != 0.f || v[2] != 0.f || v[3] != 0.f;
-    }
+    const bool lv = mx[0] != 0.f || mx[1] != 0.f || mx[2] != 0.f || mx[3] != 0.f;  // (tid >= n_rt: zeros)
     const unsigned long long bal = __ballot(lv);
     if (lane == 0) sh.balS[wave] = bal;
     __syncthreads();
@@ -2118,35 +2165,25 @@ __device__ __forceinline__ bool k4_covered(const K4Args& a, int32_t i) {
 // workgroup from the step's read-only state half; workgroup 0 writes the other
 // half and the history row. Then torch.optim.Adam (foreach, no weight decay) on
 // grads * 1 / (n_sel * accumulation_steps) when it fires; the bucket's
-// gradients are zeroed either way (zero_grad every step, :404).
+// gradients are zeroed either way (zero_grad every step, :404). The gate itself is
+// step_gate (hbk_mlp_gate.h), shared with gate_kernel and the weight-gradient kernels.
+template <bool kGateFirst>
 __global__ void __launch_bounds__(256) k4_update_kernel(K4Args a) {
   const float* st = a.state + a.parity * 8;
   const float* stats = a.G + a.n;
   // statistics read before any store (the history row copies them)
   const float n_sel = stats[0], s_loss = stats[1], s_neg = stats[2], s_fp = stats[3], s_pos = stats[4],
               s_tp = stats[5];
-  float acc_samples = st[0], acc_steps = st[1], t = st[2];
+  const float used = st[1];
   const float stepf = st[3];
   const int step = static_cast<int>(stepf);
-  float fire = 0.f, scale = 0.f, loss = 0.f;
-  const float used = acc_steps;
-  if (n_sel > 0.f) {
-    loss = s_loss / n_sel / acc_steps;
-    acc_samples += n_sel;
-    if (acc_samples < 128.f) {
-      acc_steps += 1.f;
-    } else {
-      fire = 1.f;
-      scale = 1.f / (n_sel * acc_steps);
-      acc_steps = 1.f;
-      acc_samples = 0.f;
-      t += 1.f;
-    }
-  }
+  const float loss = n_sel > 0.f ? s_loss / n_sel / used : 0.f;
+  const StepGate gate = step_gate(st[0], used, st[2], n_sel);
+  const float fire = gate.fire, scale = gate.scale, t = gate.adam_t;
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     float* nx = a.state + (1 - a.parity) * 8;
-    nx[0] = acc_samples;
-    nx[1] = acc_steps;
+    nx[0] = gate.acc_samples;
+    nx[1] = gate.acc_steps;
     nx[2] = t;
     nx[3] = stepf + 1.f;
     nx[4] = st[4];  // dropout salt of the epoch
@@ -2193,6 +2230,20 @@ __global__ void __launch_bounds__(256) k4_update_kernel(K4Args a) {
   const float bc1 = 1.f - powf(a.b1, t), bc2s = sqrtf(1.f - powf(a.b2, t));
   const float step_size = lr / bc1, inv_bc2s = 1.f / bc2s;
   const bool on = fire != 0.f;
+  const int t0 = a.wc ? a.n_tiles : 0;
+  // kGateFirst (a step run with HBK_STEP_GATE_SKIP, its slabs deferred to this update): the
+  // gate is resolved before any load. A step that does not fire has no use for its gradient,
+  // the moments or the parameters, and the slabs hold an earlier step's values (k3 / k3s left
+  // on the same decision): only the bucket ranges the slabs do not cover (k2's atomics) are
+  // zeroed; the covered ones hold zeros already, and stay so. (State half and history: above.)
+  if (kGateFirst && !on) {
+    if (static_cast<int>(blockIdx.x) < t0) return;  // (the cached matrices are covered ranges)
+    const int64_t b0 = static_cast<int64_t>(blockIdx.x) - t0, nb = static_cast<int64_t>(gridDim.x) - t0;
+    for (int64_t i = b0 * 256 + threadIdx.x; i < n4; i += nb * 256)
+      if (!k4_covered(a, static_cast<int32_t>(4 * i))) G4[i] = z4;
+    for (int64_t i = 4 * n4 + b0 * 256 + threadIdx.x; i < a.n; i += nb * 256) a.G[i] = 0.f;
+    return;
+  }
   // float4 body (the bucket, params and moments are 16-B aligned torch buffers), scalar tail
 
   // one float4: all four loads unconditional (issued together, no wait behind
@@ -2213,7 +2264,6 @@ __global__ void __launch_bounds__(256) k4_update_kernel(K4Args a) {
     }
     return p;
   };
-  const int t0 = a.wc ? a.n_tiles : 0;
   if (static_cast<int>(blockIdx.x) < t0) {  // a tile of a cached matrix
     __shared__ float tileS[kTileR][kL + 1];
     const WSeg g = a.w.s[a.tile_seg[blockIdx.x]];
@@ -2416,6 +2466,7 @@ struct StepRun {
   int flags;
   hipStream_t s;
   K1aArgs ka;
+  int gate_skip;  // the HBK_STEP_GATE_SKIP knob (flags carries the flag only while it is != 0)
 };
 
 // rows: k1a (xhat^T) | k1s (statistics and mask) of this step
@@ -2568,6 +2619,8 @@ void fill_wgrad(const StepRun& r, const float* Y0, Args& k3) {
   k3.b_off = p.ln_in.b;
   k3.part = r.ws + w.part;
   k3.pstride = w.pstride;
+  const bool skip = (r.flags & HBK_STEP_GATE_SKIP) != 0;
+  k3.gate = GateWords{skip ? r.state + 8 * r.parity : nullptr, skip ? r.bucket + p.n_params : nullptr};
 }
 
 // weight gradients: k3 | k3s, one partial slab per batch split
@@ -2612,9 +2665,11 @@ int finish_partials(const StepRun& r) {
   if (r.flags & HBK_STEP_DEFER_PARTIALS) {
     r.p.deferred_ws = r.ws;
     r.p.deferred_ks = r.pl.slabs;
+    r.p.deferred_gate = (r.flags & HBK_STEP_GATE_SKIP) ? r.gate_skip : 0;
     return HBK_OK;
   }
   r.p.deferred_ws = nullptr;
+  r.p.deferred_gate = 0;
   hipLaunchKernelGGL(k3_fold_kernel, dim3(unsigned(std::min<int64_t>((r.p.n_params / 4 + 255) / 256, 1024))), dim3(256),
                      0, r.s, make_ranges(r.p), r.ws + r.pl.ws.part, r.pl.ws.pstride, r.pl.slabs, r.bucket, r.p.n_params);
   HBK_LAUNCH_CHECK("k3_fold_kernel");
@@ -2692,8 +2747,10 @@ int mlp_fused_run(const hbk_mlp_plan& p, const float* params, const float* pool3
     }
   }
   const float keep = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
+  if (kn.gate_skip == 0) flags &= ~HBK_STEP_GATE_SKIP;  // (A/B: the step does all its work, as without the flag)
   StepRun r{p, pl, params, pool32, static_cast<const _Float16*>(pool16), y, y_stride, B, state, parity, sched,
-            sched_len, neg_weight, thr, act_thr, keep, bucket, prob, logit, ws, train, flags, s, K1aArgs{}};
+            sched_len, neg_weight, thr, act_thr, keep, bucket, prob, logit, ws, train, flags, s, K1aArgs{},
+            kn.gate_skip};
   K1aArgs& ka = r.ka;
   ka.pool32 = pool32;
   ka.pool16 = r.pool16;
@@ -2756,7 +2813,11 @@ int mlp_fused_update(const hbk_mlp_plan& p, float* params, float* bucket, float*
     k.skip_lo[sg] = static_cast<int32_t>((lo + 3) / 4);
     k.skip_hi[sg] = static_cast<int32_t>((hi + 3) / 4);
   }
+  // the step ran with HBK_STEP_GATE_SKIP: k4 resolves the gate before its loads (knob value 2:
+  // it keeps the unconditional loads and only discards, the A/B form)
+  const bool gate_first = p.deferred_ws && k.ns > 0 && p.deferred_gate == 1;
   p.deferred_ws = nullptr;
+  p.deferred_gate = 0;
   k.n_tiles = 0;
   for (int sg = 0; sg < k.w.n; ++sg)
     for (int r0 = 0; r0 < k.w.s[sg].rows && k.n_tiles < kMaxTiles; r0 += kTileR) {
@@ -2779,7 +2840,8 @@ int mlp_fused_update(const hbk_mlp_plan& p, float* params, float* bucket, float*
   k.hist = hist;
   k.hist_cap = hist_cap;
   const int64_t blocks = (k.wc ? k.n_tiles : 0) + std::min<int64_t>((p.n_params / 4 + 255) / 256, 1024);
-  hipLaunchKernelGGL(k4_update_kernel, dim3(unsigned(blocks)), dim3(256), 0, s, k);
+  hipLaunchKernelGGL(gate_first ? k4_update_kernel<true> : k4_update_kernel<false>, dim3(unsigned(blocks)), dim3(256),
+                     0, s, k);
   HBK_LAUNCH_CHECK("k4_update_kernel");
   return HBK_OK;
 }

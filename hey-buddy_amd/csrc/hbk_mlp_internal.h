@@ -36,6 +36,9 @@ struct hbk_mlp_plan {
   // slabs (deferred_ks of them) in this workspace for the next hbk_mlp_step_update
   mutable const void* deferred_ws = nullptr;
   mutable int deferred_ks = 0;
+  // ... and with HBK_STEP_GATE_SKIP (the knob of that name's value then; 0: without): on a step
+  // that does not fire the slabs are an earlier step's, and the update must not use them
+  mutable int deferred_gate = 0;
 };
 
 namespace hbk {

@@ -85,10 +85,16 @@ constexpr int kStepV2MinB = 800, kStepV2MaxCUs = 128;
 //   HBK_PRE_TILES       k1s row tiles per prefetch workgroup of k2 (>= 1)              3     call
 //   HBK_PLAN_LOG        set: print the k3s plan of each distinct batch to stderr       unset call
 //   HBK_EVAL_LAPS       0: the evaluation passes never take the lap form               on    call
+//   HBK_STEP_GATE_SKIP  0: the flag of that name is ignored (the step computes and     1     call
+//                       sums every gradient, as without it); 2: k3 / k3s leave on a
+//                       step that does not fire, k4 keeps its unconditional loads (A/B
+//                       of k4's two forms). Read by hbk_mlp_step_fwd_bwd; the update
+//                       that follows takes the form that call settled (a captured
+//                       graph keeps its capture's value)
 struct StepKnobs {
   int step = 0, v2_min_b = kStepV2MinB, k1_ks = 0;
   bool k3_wide = false, dense = false, kv_waves8 = false;
-  int k1_kc = 0, k1_rt = 0, k3_r = 0, k3_pair = -1, pre_tiles = kPreTiles2;
+  int k1_kc = 0, k1_rt = 0, k3_r = 0, k3_pair = -1, pre_tiles = kPreTiles2, gate_skip = 1;
   bool plan_log = false, eval_laps = true;
 };
 inline StepKnobs read_step_knobs() {
@@ -112,6 +118,7 @@ inline StepKnobs read_step_knobs() {
   k.k3_r = env_int("HBK_K3_R", 0);
   k.k3_pair = env_int("HBK_K3_PAIR", -1);
   k.pre_tiles = env_int("HBK_PRE_TILES", kPreTiles2);
+  k.gate_skip = env_int("HBK_STEP_GATE_SKIP", 1);
   k.plan_log = getenv("HBK_PLAN_LOG") != nullptr;
   const char* laps = getenv("HBK_EVAL_LAPS");
   k.eval_laps = !(laps && laps[0] == '0');

@@ -652,7 +652,9 @@ class WakeWordTrainer(Trainer):
 
         # Each step also gathers + normalises the NEXT step's rows inside its own
         # launches (prefetch_next); only the first step of this call gathers its own.
-        # One process: the weight-gradient slabs go straight to the update (no all-reduce between).
+        # One process: the weight-gradient slabs go straight to the update (no all-reduce between),
+        # and a step whose update will not fire computes none (gate_skip: nothing touches the
+        # state or the statistics between the two calls below).
         defer = not distributed.reduces()
         # HBK_NO_PREFETCH=1 (A/B): every step gathers its own rows in a k1a launch
         pre = os.environ.get("HBK_NO_PREFETCH") is None
@@ -662,7 +664,7 @@ class WakeWordTrainer(Trainer):
                               idx_stride=B, y_stride=y_stride, sched=sched, threshold=threshold,
                               activation_threshold=activation_threshold, dropout_p=p, seed=self._seed_base,
                               workspace=ws, xhat_ready=ready and pre, prefetch_next=pre, idx_steps=S_all,
-                              weights_ready=ready, defer_partials=defer)
+                              weights_ready=ready, defer_partials=defer, gate_skip=defer)
             distributed.reduce_bucket(self._bucket)
             plan.step_update(flat, self._bucket, self._m, self._v, self._fstate, parity, sched=sched,
                              beta1=BETAS[0], beta2=BETAS[1], eps=EPS, history=history, workspace=ws)
@@ -680,7 +682,7 @@ class WakeWordTrainer(Trainer):
             """The captured graph of n (even) steps from the current parity."""
             par0 = self._parity
             key = ("indexed", n, par0, B, y_stride, float(threshold), float(activation_threshold), float(p),
-                   defer, pre, ptrs, torch.cuda.current_stream(dev).cuda_stream)
+                   defer, pre, os.environ.get("HBK_STEP_GATE_SKIP"), ptrs, torch.cuda.current_stream(dev).cuda_stream)
 
             def steps() -> None:
                 for j in range(n):

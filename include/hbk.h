@@ -310,11 +310,31 @@ int hbk_mlp_gate_adam(const hbk_mlp_plan* plan, float* params, const float* buck
  *     get this workspace (it fails otherwise) and must follow with nothing that
  *     reads the bucket in between (one process: no all-reduce);
  *   without it: into the bucket at the end of this call (for the data-parallel
- *     all-reduce, or an update without the workspace). */
+ *     all-reduce, or an update without the workspace).
+ * A step whose update does not fire (fewer than 128 accumulated selected rows)
+ * drops its gradient: the reference never computes one (trainer.py:443-465),
+ * and hbk_mlp_step_update zeroes the bucket either way.
+ *   flags & HBK_STEP_GATE_SKIP (only with HBK_STEP_DEFER_PARTIALS, HBK_ERR_ARG
+ *     otherwise): the weight-gradient kernels read the step's state half and the
+ *     bucket's n_sel once the chain kernel has made it final, decide the gate by
+ *     the update's own rule, and on a step that will not fire write no slab; the
+ *     update then decides first and, on such a step, only zeroes the bucket and
+ *     writes the state half and the history row: params, m, v and the weight
+ *     cache are not touched, the slabs (an earlier step's) not read. The caller
+ *     promises that the next hbk_mlp_step_update gets the same `state` and
+ *     `parity` and the bucket's statistics unchanged, i.e. that nothing writes
+ *     either in between (so: one process, no all-reduce of the statistics; a
+ *     caller that edits `state` between the two calls must not set the flag).
+ *     The decision is read from device memory, so a replayed hipGraph follows
+ *     each step. Results are those without the flag (bit for bit where the
+ *     step's results are: the chain kernel's float atomics sum in any order).
+ *     HBK_STEP_GATE_SKIP=0 in the environment makes the library ignore the flag
+ *     (read by every hbk_mlp_step_fwd_bwd call; the update follows that call). */
 #define HBK_STEP_XHAT_READY 1
 #define HBK_STEP_PREFETCH_NEXT 2
 #define HBK_STEP_WEIGHTS_READY 4
 #define HBK_STEP_DEFER_PARTIALS 8
+#define HBK_STEP_GATE_SKIP 16
 int hbk_mlp_fused_supported(const hbk_mlp_plan* plan, int32_t* supported);
 /* 1 = k1a/k1b/k3 (v1), 2 = k1s/k1c/k3s (v2): the variant hbk_mlp_step_fwd_bwd
  * takes for `batch` rows on `stream`. Fused plans only. */

@@ -3,7 +3,9 @@
 Runs bench.py's main() with the arguments given after ``--`` (default: the
 headline, config 5, 5 + 2 steps) and keeps every history buffer the timed
 path hands to train_indexed; after the run it reads column 0 (n_sel) of the
-last chunk's rows and prints its distribution, with ceil(n_sel / 16) (the
+last chunk's rows and column 2 (fired: the share of steps whose update ran,
+and how firing and non-firing steps follow each other) and prints n_sel's
+distribution, with ceil(n_sel / 16) (the
 fewest 16-row tiles that hold them) and ceil(n_sel / 32) (the 32-row steps
 of a row-compacted walk) per train step. The history has no per-row data, so
 the live tiles themselves are counted by classifying the chunk's last 200
@@ -78,7 +80,12 @@ def main() -> None:
             "n_neg_sel": dist(h[:, 4]), "n_pos_sel": dist(h[:, 6]),
             "live_16row_tiles_lower_bound": dist(tiles_lo), "dense_16row_tiles": -(-B // 16),
             "compacted_32row_steps": dist(steps32), "dense_32row_steps": -(-B // 32),
-            "fired_share": round(float((h[:, 2] > 0).mean()), 3)})
+            # column 2 (fired): the steps whose update ran; the others' gradients are dropped
+            # (the < 128-sample gate). pairs: (this step, the next) fired -> count
+            "fired_share": round(float((h[:, 2] > 0).mean()), 3), "fired_steps": int((h[:, 2] > 0).sum()),
+            "n_sel_below_128_share": round(float((n < 128).mean()), 3),
+            "fired_pairs": {f"{int(a)}{int(b)}": int(((h[:-1, 2] > 0) == a).__and__((h[1:, 2] > 0) == b).sum())
+                            for a in (0, 1) for b in (0, 1)}})
         if pool32 is not None and pool16 is not None:
             rf = reforward(tr, idx, y, pool32, pool16, min(200, idx.shape[0]))
             res["buffers"][-1]["reforward_last_200_batches_final_weights"] = {
