@@ -166,6 +166,69 @@ __device__ __forceinline__ int opaque_tid() {
   return t;
 }
 
+// Optional source view of a kernel's input clips (placement on first touch):
+// clip i with pre[i] >= 0 has not been placed yet and is read from its source
+// row src[i] (len[i] valid samples) through load_placed; pre[i] < 0 (or pre
+// NULL): the row is placed, the kernel reads its x as without a view.
+struct SrcView {
+  const float* src;
+  int64_t stride;
+  const int32_t* len;
+  const int32_t* pre;
+};
+
+// the entry points' view arguments: all NULL / 0 (no view) or all given
+inline int src_view(const float* src, int64_t stride, const int32_t* len, const int32_t* pre, SrcView& v) {
+  v = SrcView{nullptr, 0, nullptr, nullptr};
+  if (!src && !len && !pre) return HBK_OK;
+  if (!src || !len || !pre) return arg_error("source view needs src, src_len and src_pre");
+  if (stride < 0) return arg_error("negative src_stride");
+  v = SrcView{src, stride, len, pre};
+  return HBK_OK;
+}
+
+// Sample t of a clip placed on first touch (place_kernel's load, shared with the
+// kernels that read a source row through its placement instead of the placed
+// row): row[t - pre] for pre <= t < pre + n, else 0, where n = min(len, T). The
+// load is unconditional (its index clamped into the row, the value selected
+// after), so a thread's loads are in flight together. row[0] must be readable
+// even when n <= 0 (the caller passes any valid row then; every sample is 0).
+// 32-bit byte offset from a uniform base: global_load's saddr form.
+// (In two halves for a kernel that loads a clip ahead and consumes it later: the select
+// then sits at the use, not behind the load.)
+__device__ __forceinline__ uint32_t placed_index(int pre, int n, int t) {
+  return static_cast<uint32_t>(min(max(t - pre, 0), max(n - 1, 0)));
+}
+__device__ __forceinline__ float placed_select(float v, int pre, int n, int t) {
+  const int u = t - pre;
+  return (u >= 0 && u < n) ? v : 0.f;
+}
+__device__ __forceinline__ float load_placed(const float* row, int pre, int n, int t) {
+  const float v = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(row) + (placed_index(pre, n, t) << 2));
+  return placed_select(v, pre, n, t);
+}
+
+// A wave's 64 consecutive samples w0 .. w0 + 63 (w0 uniform, a multiple of 64) of such a
+// clip lie inside the source clip (1), outside it (0) or across one of its ends (2). The
+// class is uniform and depends on (pre, n, w0) alone, so a branch on it waits on no load;
+// a wave inside the clip has nothing to select (the tanh and augment kernels are bound by
+// their VALU work: a select on every sample showed in their times).
+__device__ __forceinline__ int placed_class(int pre, int n, int w0) {
+  const int rel = w0 - pre;
+  return (rel >= 0 && rel + 63 < n) ? 1 : ((rel + 63 < 0 || rel >= n) ? 0 : 2);
+}
+// sample w0 + lane of the clip: load_placed's value (the same load where one is needed)
+__device__ __forceinline__ float load_placed_wave(const float* row, int pre, int n, int w0, int lane) {
+  // (a wave outside the clip loads nothing; the other two classes share one load
+  // instruction: a second one behind a branch made the compiler wait for every load in
+  // flight before it)
+  const int cls = placed_class(pre, n, w0);
+  if (cls == 0) return 0.f;
+  const uint32_t i = cls == 1 ? static_cast<uint32_t>(w0 - pre + lane) : placed_index(pre, n, w0 + lane);
+  const float v = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(row) + (i << 2));
+  return cls == 1 ? v : placed_select(v, pre, n, w0 + lane);
+}
+
 // two block sums in one barrier round (red holds 2 x 16 wave partials)
 __device__ __forceinline__ void block_sum2(float& a, float& b, float* red) {
   a = wave_sum(a);

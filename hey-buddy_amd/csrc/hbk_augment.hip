@@ -235,7 +235,19 @@ struct AugArgs {
   int64_t c_group;
   const float* c_gbuf;      // [groups][16000]: the coloured second x 8000
   const float* c_grms;      // [groups], NULL: no group path
+  // placement on first touch (hbk_reverb_plan_set_source; pre NULL: none): a clip with
+  // pre >= 0 is read from its source row through load_placed instead of from x. A clip
+  // coloured by colored_noise_kernel (colored_mode 2) is placed: that kernel reads x.
+  SrcView view;
 };
+
+// (pre, n = min(len, T)) of a clip read through the view, packed into one uniform word
+// (both < 2^15: T = 23,040) so that the read-ahead costs this kernel one SGPR; < 0: placed
+__device__ __forceinline__ int view_word(const AugArgs& a, int64_t clip) {
+  if (!a.view.pre) return -1;
+  const int pre = a.view.pre[clip], len = a.view.len[clip];  // (two independent loads: one latency)
+  return pre < 0 ? -1 : (min(pre, kT) << 16) | max(min(len, kT), 0);
+}
 
 // 0: no colored noise, 1: mixed in augment_kernel's prologue, 2: coloured by
 // colored_noise_kernel into out (uniform per clip)
@@ -272,7 +284,11 @@ __global__ void __launch_bounds__(kThreads) augment_kernel(AugArgs a) {
   // (noff: the clip's noise offset, read well before, so that no branch waits
   // on a load queued behind these; vmcnt retires loads in order)
   // (cmode: colored_mode of the clip, read ahead like noff; 2 = read the clip from out)
-  auto prefetch = [&](int64_t clip, int64_t noff, int cmode) {
+  // (vw: view_word of the clip, read ahead like them; >= 0: the loads go to the source row,
+  // at place_kernel's clamped indices, one load per slot whatever the wave's placed_class (a
+  // second load instruction per slot behind a branch made the compiler wait for every load in
+  // flight before it); the clip's loop turn selects the zeros around the source clip)
+  auto prefetch = [&](int64_t clip, int64_t noff, int cmode, int vw) {
     // uniform base + 32-bit per-lane offsets from an opaque thread id (keeps
     // the 46 per-load addresses from being hoisted out of the clip loop)
     const int t = opaque_tid();
@@ -285,8 +301,16 @@ __global__ void __launch_bounds__(kThreads) augment_kernel(AugArgs a) {
     auto at = [](const float* base, uint32_t i) {
       return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + (i << 2));
     };
+    if (vw >= 0 && cmode != 2) {
+      const int pre = vw >> 16, n = vw & 0xFFFF;
+      // (an empty source clip: any readable row, every sample is selected to 0)
+      const float* s = n > 0 ? a.view.src + clip * a.view.stride : x;
 #pragma unroll
-    for (int u = 0; u < kPer; ++u) xr[u] = at(x, static_cast<uint32_t>(min(t + u * kThreads, kT - 1)));
+      for (int u = 0; u < kPer; ++u) xr[u] = at(s, placed_index(pre, n, min(t + u * kThreads, kT - 1)));
+    } else {
+#pragma unroll
+      for (int u = 0; u < kPer; ++u) xr[u] = at(x, static_cast<uint32_t>(min(t + u * kThreads, kT - 1)));
+    }
     if (noff >= 0) {
       const uint32_t rlen = static_cast<uint32_t>(a.ring_len), r0 = static_cast<uint32_t>(noff);
 #pragma unroll
@@ -297,7 +321,9 @@ __global__ void __launch_bounds__(kThreads) augment_kernel(AugArgs a) {
       }
     }
   };
-  if (blockIdx.x < a.n_clips) prefetch(blockIdx.x, a.noise_off[blockIdx.x], colored_mode(a, blockIdx.x));
+  // (the clip's own word is carried from the turn that read it ahead: no load at the loop's top)
+  int vw_cur = blockIdx.x < a.n_clips ? __builtin_amdgcn_readfirstlane(view_word(a, blockIdx.x)) : -1;
+  if (blockIdx.x < a.n_clips) prefetch(blockIdx.x, a.noise_off[blockIdx.x], colored_mode(a, blockIdx.x), vw_cur);
   unsigned long long ph_t0 = 0;
 #ifdef HBK_PHASE_TIMING
   ph_t0 = __builtin_amdgcn_s_memtime();
@@ -313,7 +339,19 @@ __global__ void __launch_bounds__(kThreads) augment_kernel(AugArgs a) {
     const int64_t noff_next = __builtin_amdgcn_readfirstlane(static_cast<int>(next ? a.noise_off[clip + gridDim.x] : -1));
     const int cmode = __builtin_amdgcn_readfirstlane(colored_mode(a, clip));
     const int cmode_next = __builtin_amdgcn_readfirstlane(next ? colored_mode(a, clip + gridDim.x) : 0);
+    const int vw = vw_cur;
+    const int vw_next = __builtin_amdgcn_readfirstlane(next ? view_word(a, clip + gridDim.x) : -1);
+    vw_cur = vw_next;
     float ex = 0.f, aa = 0.f;
+    if (vw >= 0 && cmode != 2) {  // read through the view: the zeros around the source clip (a wave
+      // whose 64 samples lie inside it has none to select: placed_class, uniform)
+      const int t = opaque_tid(), pre = vw >> 16, n = vw & 0xFFFF;
+      const int w0 = __builtin_amdgcn_readfirstlane(t & ~63);
+#pragma unroll
+      for (int u = 0; u < kPer; ++u)
+        if (placed_class(pre, n, w0 + u * kThreads) != 1)
+          xr[u] = placed_select(xr[u], pre, n, min(w0 + u * kThreads + (t & 63), kT - 1));
+    }
     if (cmode == 1) {
       // colored noise (the group path), in colored_mix_kernel's per-thread order and block
       // sum: bit-identical to hbk_colored_noise_ws followed by hbk_augment
@@ -373,7 +411,7 @@ __global__ void __launch_bounds__(kThreads) augment_kernel(AugArgs a) {
     HBK_APH(3);
     float* out = a.out + clip * a.out_stride;
     if (sp < 0) {  // no reverb: each thread stores the samples it wrote
-      if (next) prefetch(clip + gridDim.x, noff_next, cmode_next);
+      if (next) prefetch(clip + gridDim.x, noff_next, cmode_next, vw_next);
       for (int s = opaque_tid(); s < kT; s += kThreads) out[s] = zf[s];
       __syncthreads();
       continue;
@@ -444,7 +482,7 @@ __global__ void __launch_bounds__(kThreads) augment_kernel(AugArgs a) {
     HBK_APH(9);
     // 5) inverse FFT (permuted -> natural), 1/M
     transform<true>(z, thi, tlo, ph_t0, 10);
-    if (next) prefetch(clip + gridDim.x, noff_next, cmode_next);
+    if (next) prefetch(clip + gridDim.x, noff_next, cmode_next, vw_next);
     float ay = 0.f;
     for (int s = opaque_tid(); s < kT; s += kThreads) ay += fabsf(zf[s]);
     const float a_out = block_sum(ay, red) / kT / kM;
@@ -1032,6 +1070,9 @@ struct hbk_reverb_plan {
   const float2* thi8 = nullptr;  // colored noise: W_8000^(100 h), W_8000^l, W_16000^k (k <= 4000)
   const float2* tlo8 = nullptr;
   const float2* twn16 = nullptr;
+  // placement on first touch: the source view hbk_augment / hbk_augment_colored read their
+  // clips through (hbk_reverb_plan_set_source; pre NULL: none)
+  hbk::SrcView view = {nullptr, 0, nullptr, nullptr};
 };
 
 extern "C" {
@@ -1085,6 +1126,12 @@ int hbk_reverb_plan_destroy(hbk_reverb_plan* p) {
   return HBK_OK;
 }
 
+int hbk_reverb_plan_set_source(hbk_reverb_plan* p, const float* src, int64_t src_stride, const int32_t* src_len,
+                               const int32_t* src_pre) {
+  if (!p) return hbk::arg_error("plan is NULL");
+  return hbk::src_view(src, src_stride, src_len, src_pre, p->view);
+}
+
 int hbk_reverb_spectrum(const hbk_reverb_plan* p, const float* kernels, int64_t n_kernels, int64_t stride,
                         float* spectra, void* stream) {
   using namespace hbk;
@@ -1126,6 +1173,7 @@ static int augment_args(const hbk_reverb_plan* p, const float* x, int64_t n_clip
   a.thi = p->thi;
   a.tlo = p->tlo;
   a.twn = p->twn;
+  a.view = p->view;
   return HBK_OK;
 }
 

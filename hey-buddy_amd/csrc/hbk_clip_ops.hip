@@ -26,6 +26,7 @@ struct TanhArgs {
   const float* amount;  // per clip; NaN = clip unchanged
   const int32_t* idx;   // NULL: every clip; else the n_entries listed clip rows (balanced launch)
   int64_t n_entries;
+  SrcView view;         // pre NULL: none (a clip read through it has a non-NaN amount)
 };
 
 // |x| bits of slot u (u < kPer), or ~0 past the end of the clip (above every value);
@@ -57,7 +58,18 @@ tanh_distortion_kernel(TanhArgs a) {
     // uniform base + 32-bit byte offsets (global_load's saddr form): one VGPR per
     // address instead of a hoisted 64-bit pointer per slot
     float xr[kPer];
-    {
+    // (pre: uniform, read with amt before any load; a clip placed on first touch comes from
+    // its source row, the others from x as before)
+    // (len: loaded with pre, not behind the branch on it: one latency)
+    const int pre = a.view.pre ? a.view.pre[clip] : -1, len = a.view.pre ? a.view.len[clip] : 0;
+    if (pre >= 0) {
+      const int n = min(len, kT);
+      const float* row = n > 0 ? a.view.src + clip * a.view.stride : x;
+      const int t = opaque_tid();
+      const int w0 = __builtin_amdgcn_readfirstlane(t & ~63);
+#pragma unroll
+      for (int u = 0; u < kPer; ++u) xr[u] = load_placed_wave(row, pre, n, w0 + u * kThreads, t & 63);
+    } else {
     const int t = opaque_tid();
 #pragma unroll
     for (int u = 0; u < kPer; ++u) {
@@ -167,20 +179,25 @@ tanh_distortion_kernel(TanhArgs a) {
 constexpr int kPlaceSpan = 4096;
 __global__ void __launch_bounds__(256) place_kernel(const float* __restrict__ src, int64_t src_stride,
                                                     const int32_t* __restrict__ src_len,
-                                                    const int32_t* __restrict__ pre, float* __restrict__ out,
+                                                    const int32_t* __restrict__ pre,
+                                                    const int32_t* __restrict__ idx, float* __restrict__ out,
                                                     int64_t out_stride, int64_t n_clips, int T) {
   // workgroup b takes (clip, span) item b (one 4,096-sample span of one clip; a 1-D grid, so
   // no 65,535-clip launch limit); every load is unconditional (clamped into the clip, zeroed by
   // a select), so a thread's 16 loads are in flight together instead of each behind its own
   // branch
+  // (idx: the clip rows to place, n_clips of them; NULL: rows 0 .. n_clips - 1. The other
+  // rows of out are placed by their first consumer, which loads what is loaded here:
+  // load_placed, hbk_aug_dev.h.)
   const int spans = (T + kPlaceSpan - 1) / kPlaceSpan;
   const int64_t items = n_clips * spans;
   constexpr int kR = kPlaceSpan / 1024;
   // (measured: the same 3.1 ms per 100 k clips, 4.85 TB/s, as the round-4 2-D grid with
   // predicated loads, tools/probe_place.py: the kernel is bound by HBM's write rate)
   for (int64_t it = blockIdx.x; it < items; it += gridDim.x) {  // (one pass: grid = items)
-    const int64_t clip = it / spans;
-    const int sp = static_cast<int>(it - clip * spans);
+    const int64_t e = it / spans;
+    const int sp = static_cast<int>(it - e * spans);
+    const int64_t clip = idx ? idx[e] : e;
     const int p = pre[clip];
     const int n = min(src_len[clip], T);
     const int last = max(n - 1, 0);
@@ -225,6 +242,7 @@ struct EqArgs {
   float* out;
   int64_t out_stride;
   int64_t n;
+  SrcView view;  // pre NULL: none
 };
 
 // Systolic over the cascade: a wave filters 8 clips, 8 lanes per clip; lane
@@ -235,7 +253,10 @@ struct EqArgs {
 // cascade (float32 between sections), so the result is bitwise that of the
 // sequential filter; eight times as many waves fill the chip (the filter is
 // sequential in time, so one lane per clip left most SIMDs idle). A clip whose
-// coefficients are NaN passes through an identity cascade (a copy).
+// coefficients are NaN passes through an identity cascade (a copy). A clip
+// placed on first touch (a.view) loads its tile samples from the source row
+// with scalar loads instead of the two aligned float4 (the same values:
+// load_tile below).
 constexpr int kEqClips = 8;  // clips per wave
 __global__ void __launch_bounds__(64) eq_kernel(EqArgs a) {
   constexpr int kRow = kEqTile + 4;  // 16-B aligned rows (b128 reads / writes of 8 steps)
@@ -257,8 +278,34 @@ __global__ void __launch_bounds__(64) eq_kernel(EqArgs a) {
   const float* xl = a.x + clip_l * a.x_stride;
   float* ol = a.out + clip_l * a.out_stride;
   const bool store_l = j0 + lc < a.n;
-  float4 p0 = *reinterpret_cast<const float4*>(xl + 4 * lq);
-  float4 p1 = *reinterpret_cast<const float4*>(xl + 32 + 4 * lq);
+  // (pre_l / n_l are read once, here: no tile load waits on them)
+  const int pre_l = a.view.pre ? a.view.pre[clip_l] : -1, len_l = a.view.pre ? a.view.len[clip_l] : 0;
+  const int n_l = pre_l >= 0 ? min(len_l, kT) : 0;
+  const float* sl = n_l > 0 ? a.view.src + clip_l * a.view.stride : xl;
+  float4 p0, p1;
+  auto load_tile = [&](int t) {  // samples t + 4 lq .. + 3 and t + 32 + 4 lq .. + 3 of the lane's clip
+    // (the branches depend on pre_l / n_l / t alone; a lane's eight samples lie inside the
+    // source clip, outside it, or across one of its ends: the last case alone pays for the
+    // clamps and selects, which this kernel, bound by its VALU work, would feel on every tile)
+    const int u0 = t + 4 * lq - pre_l;
+    if (pre_l >= 0 && u0 >= 0 && u0 + 35 < n_l) {
+      const float* q = sl + u0;
+      p0 = float4{q[0], q[1], q[2], q[3]};
+      p1 = float4{q[32], q[33], q[34], q[35]};
+    } else if (pre_l >= 0 && (u0 + 35 < 0 || u0 >= n_l)) {
+      p0 = p1 = float4{0.f, 0.f, 0.f, 0.f};
+    } else if (pre_l >= 0) {
+      const int ta = t + 4 * lq, tb = ta + 32;
+      p0 = float4{load_placed(sl, pre_l, n_l, ta), load_placed(sl, pre_l, n_l, ta + 1),
+                  load_placed(sl, pre_l, n_l, ta + 2), load_placed(sl, pre_l, n_l, ta + 3)};
+      p1 = float4{load_placed(sl, pre_l, n_l, tb), load_placed(sl, pre_l, n_l, tb + 1),
+                  load_placed(sl, pre_l, n_l, tb + 2), load_placed(sl, pre_l, n_l, tb + 3)};
+    } else {
+      p0 = *reinterpret_cast<const float4*>(xl + t + 4 * lq);
+      p1 = *reinterpret_cast<const float4*>(xl + t + 32 + 4 * lq);
+    }
+  };
+  load_tile(0);
   float prev = 0.f;
   for (int t0 = 0; t0 <= kT; t0 += kEqTile) {  // the last tile only drains the pipeline
     tin[lc][4 * lq] = p0.x;
@@ -271,8 +318,7 @@ __global__ void __launch_bounds__(64) eq_kernel(EqArgs a) {
     tin[lc][32 + 4 * lq + 3] = p1.w;
     __syncthreads();
     const int tn = min(t0 + kEqTile, kT - kEqTile);  // next tile (clamped: the drain re-reads the last)
-    p0 = *reinterpret_cast<const float4*>(xl + tn + 4 * lq);
-    p1 = *reinterpret_cast<const float4*>(xl + tn + 32 + 4 * lq);
+    load_tile(tn);
     // 8 steps per group: their section-0 inputs read ahead (two b128 reads, one
     // wait), section 6's outputs written after (branch-free steps in between)
     for (int st0 = 0; st0 < kEqTile; st0 += 8) {
@@ -316,26 +362,35 @@ __global__ void __launch_bounds__(64) eq_kernel(EqArgs a) {
 
 extern "C" {
 
-int hbk_place_clips(const float* src, int64_t n_clips, int64_t src_stride, const int32_t* src_len,
-                    const int32_t* pre, float* out, int64_t out_stride, int64_t T, void* stream) {
+int hbk_place_clips_idx(const float* src, int64_t n_clips, int64_t src_stride, const int32_t* src_len,
+                        const int32_t* pre, const int32_t* idx, int64_t n_entries, float* out, int64_t out_stride,
+                        int64_t T, void* stream) {
   using namespace hbk;
-  if (n_clips < 0) return arg_error("negative n_clips");
-  if (n_clips == 0) return HBK_OK;
+  if (n_clips < 0 || (idx && n_entries < 0)) return arg_error("negative count");
+  const int64_t n_rows = idx ? n_entries : n_clips;  // rows placed: the listed ones, or all
+  if (n_rows == 0) return HBK_OK;
   if (!src || !src_len || !pre || !out) return arg_error("NULL pointer");
   if (T <= 0 || T % 4 || T > (int64_t(1) << 30)) return arg_error("T must be a positive multiple of 4");
   if (out_stride < T || out_stride % 4 || (reinterpret_cast<uintptr_t>(out) & 15))
     return arg_error("out rows must be 16-B aligned with stride >= T");
-  const int64_t items = n_clips * ((T + kPlaceSpan - 1) / kPlaceSpan);
+  const int64_t items = n_rows * ((T + kPlaceSpan - 1) / kPlaceSpan);
   if (items >= (int64_t(1) << 31)) return arg_error("too many clips for one launch");
   const int64_t blocks = items;
   hipLaunchKernelGGL(place_kernel, dim3(unsigned(blocks)), dim3(256), 0, as_stream(stream), src, src_stride, src_len,
-                     pre, out, out_stride, n_clips, int(T));
+                     pre, idx, out, out_stride, n_rows, int(T));
   HBK_LAUNCH_CHECK("place_kernel");
   return HBK_OK;
 }
 
-int hbk_tanh_distortion(const float* x, int64_t n_clips, int64_t x_stride, const float* amount,
-                        const int32_t* idx, int64_t n_entries, float* out, int64_t out_stride, void* stream) {
+int hbk_place_clips(const float* src, int64_t n_clips, int64_t src_stride, const int32_t* src_len,
+                    const int32_t* pre, float* out, int64_t out_stride, int64_t T, void* stream) {
+  return hbk_place_clips_idx(src, n_clips, src_stride, src_len, pre, nullptr, 0, out, out_stride, T, stream);
+}
+
+int hbk_tanh_distortion_src(const float* x, int64_t n_clips, int64_t x_stride, const float* amount,
+                            const int32_t* idx, int64_t n_entries, float* out, int64_t out_stride,
+                            const float* src, int64_t src_stride, const int32_t* src_len, const int32_t* src_pre,
+                            void* stream) {
   using namespace hbk;
   if (n_clips < 0) return arg_error("negative n_clips");
   if (n_clips == 0) return HBK_OK;
@@ -350,6 +405,8 @@ int hbk_tanh_distortion(const float* x, int64_t n_clips, int64_t x_stride, const
   a.amount = amount;
   a.idx = idx;
   a.n_entries = idx ? n_entries : n_clips;
+  const int st = src_view(src, src_stride, src_len, src_pre, a.view);
+  if (st != HBK_OK) return st;
   if (a.n_entries <= 0) return n_entries < 0 ? arg_error("negative n_entries") : HBK_OK;
   const int64_t blocks = std::min<int64_t>(a.n_entries, persistent_blocks(2, stream));
   hipLaunchKernelGGL(tanh_distortion_kernel, dim3(unsigned(blocks)), dim3(kThreads), 0, as_stream(stream), a);
@@ -357,8 +414,15 @@ int hbk_tanh_distortion(const float* x, int64_t n_clips, int64_t x_stride, const
   return HBK_OK;
 }
 
-int hbk_seven_band_eq(const float* x, int64_t n_clips, int64_t x_stride, const double* coef, const int32_t* idx,
-                      int64_t n_entries, float* out, int64_t out_stride, void* stream) {
+int hbk_tanh_distortion(const float* x, int64_t n_clips, int64_t x_stride, const float* amount,
+                        const int32_t* idx, int64_t n_entries, float* out, int64_t out_stride, void* stream) {
+  return hbk_tanh_distortion_src(x, n_clips, x_stride, amount, idx, n_entries, out, out_stride, nullptr, 0, nullptr,
+                                 nullptr, stream);
+}
+
+int hbk_seven_band_eq_src(const float* x, int64_t n_clips, int64_t x_stride, const double* coef, const int32_t* idx,
+                          int64_t n_entries, float* out, int64_t out_stride, const float* src, int64_t src_stride,
+                          const int32_t* src_len, const int32_t* src_pre, void* stream) {
   using namespace hbk;
   if (n_clips < 0 || n_entries < 0) return arg_error("negative count");
   if (!idx) n_entries = n_clips;
@@ -375,10 +439,18 @@ int hbk_seven_band_eq(const float* x, int64_t n_clips, int64_t x_stride, const d
   a.out = out;
   a.out_stride = out_stride;
   a.n = n_entries;
+  const int st = src_view(src, src_stride, src_len, src_pre, a.view);
+  if (st != HBK_OK) return st;
   hipLaunchKernelGGL(eq_kernel, dim3(unsigned((n_entries + kEqClips - 1) / kEqClips)), dim3(64), 0,
                      as_stream(stream), a);
   HBK_LAUNCH_CHECK("eq_kernel");
   return HBK_OK;
+}
+
+int hbk_seven_band_eq(const float* x, int64_t n_clips, int64_t x_stride, const double* coef, const int32_t* idx,
+                      int64_t n_entries, float* out, int64_t out_stride, void* stream) {
+  return hbk_seven_band_eq_src(x, n_clips, x_stride, coef, idx, n_entries, out, out_stride, nullptr, 0, nullptr,
+                               nullptr, stream);
 }
 
 }  // extern "C"

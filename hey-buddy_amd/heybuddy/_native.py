@@ -98,6 +98,13 @@ _PROTOS = {
                                  ctypes.c_int32, _vp, _c_int64, _vp, _c_int64, _vp]),
     "hbk_seven_band_eq": (_c_int, [_vp, _c_int64, _c_int64, _vp, _vp, _c_int64, _vp, _c_int64, _vp]),
     "hbk_place_clips": (_c_int, [_vp, _c_int64, _c_int64, _vp, _vp, _vp, _c_int64, _c_int64, _vp]),
+    "hbk_place_clips_idx": (_c_int, [_vp, _c_int64, _c_int64, _vp, _vp, _vp, _c_int64, _vp, _c_int64, _c_int64,
+                                     _vp]),
+    "hbk_seven_band_eq_src": (_c_int, [_vp, _c_int64, _c_int64, _vp, _vp, _c_int64, _vp, _c_int64,
+                                       _vp, _c_int64, _vp, _vp, _vp]),
+    "hbk_tanh_distortion_src": (_c_int, [_vp, _c_int64, _c_int64, _vp, _vp, _c_int64, _vp, _c_int64,
+                                         _vp, _c_int64, _vp, _vp, _vp]),
+    "hbk_reverb_plan_set_source": (_c_int, [_vp, _vp, _c_int64, _vp, _vp]),
     "hbk_mlp_set_step_scalars": (_c_int, [_vp, _vp]),
     "hbk_mlp_plan_create": (_c_int, [ctypes.c_int32] * 4 + [ctypes.POINTER(_vp)]),
     "hbk_mlp_plan_destroy": (_c_int, [_vp]),

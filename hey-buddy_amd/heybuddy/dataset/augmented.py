@@ -66,7 +66,7 @@ from heybuddy.constants import (DEFAULT_AUGMENT_BACKGROUND_NOISE_MAX_SNR_DB,
                                 DEFAULT_AUGMENT_GAIN_MIN_DB, DEFAULT_AUGMENT_GAIN_PROB,
                                 DEFAULT_AUGMENT_REVERB_PROB, DEFAULT_AUGMENT_SEVEN_BAND_GAIN_DB,
                                 DEFAULT_AUGMENT_SEVEN_BAND_PROB)
-from heybuddy.kernels import ReverbPlan, pitch_shift, place_clips, seven_band_eq, tanh_distortion
+from heybuddy.kernels import ReverbPlan, SourceView, pitch_shift, place_clips, seven_band_eq, tanh_distortion
 
 __all__ = ["AugmentedAudioGenerator", "BatchAugmenter", "SourceOrder", "bandstop_cutoffs", "eq_coefficients",
            "eq_parameters", "hf_shuffle_permutation", "source_plan", "target_length_offset", "target_length_offsets",
@@ -200,6 +200,32 @@ def fast_shifts(sample_rate: int = 16000, semitones: float = DEFAULT_AUGMENT_PIT
     products = {prod(c) for r in range(1, len(fac) + 1) for c in combinations(fac, r)}
     lo, hi = Fraction(2.0 ** (-semitones / 12.0)), Fraction(2.0 ** (semitones / 12.0))
     return sorted({Fraction(i, j) for i in products for j in products if lo <= Fraction(i, j) <= hi} - {1})
+
+
+# Placement on first touch: the kernel that first reads a clip's placed row can read
+# the source row through the placement instead (the same loads), so place_kernel
+# writes only the clips none of the three kernels below reads first.
+ROUTE_PLACE, ROUTE_EQ, ROUTE_TANH, ROUTE_AUGMENT = 0, 1, 2, 3
+
+
+def first_touch_enabled() -> bool:
+    """HBK_PLACE_FIRST_TOUCH=0 restores the place-everything path (A/B runs)."""
+    return os.environ.get("HBK_PLACE_FIRST_TOUCH", "1") != "0"
+
+
+def first_touch_routes(eq_on: np.ndarray, tanh_on: np.ndarray, placed_first: np.ndarray) -> np.ndarray:
+    """Each clip's first consumer, int8 [n], from the chain's order (EQ, tanh,
+    pitch shift, band-stop, colored noise, augment): a clip in the EQ list is
+    read by eq_kernel (ROUTE_EQ); else one whose tanh coin came up by
+    tanh_distortion_kernel (ROUTE_TANH); else one that no kernel without the
+    source view reads first (``placed_first``: its batch drew a pitch shift or a
+    band-stop, or colored_noise_kernel colours it) by augment_kernel
+    (ROUTE_AUGMENT); every other clip is placed by place_kernel (ROUTE_PLACE)."""
+    eq_on, tanh_on, placed_first = (np.asarray(a, dtype=bool) for a in (eq_on, tanh_on, placed_first))
+    route = np.where(placed_first, ROUTE_PLACE, ROUTE_AUGMENT).astype(np.int8)
+    route[tanh_on] = ROUTE_TANH
+    route[eq_on] = ROUTE_EQ
+    return route
 
 
 class BatchAugmenter:
@@ -415,27 +441,65 @@ class BatchAugmenter:
         if not np.isnan(colored_snr).all():
             colored = (torch.from_numpy(colored_fd), torch.from_numpy(colored_snr),
                        int(torch.randint(0, 2 ** 62, (1,)).item()))
-        return {"n": n, "noise_off": torch.from_numpy(noise_off), "spec_idx": torch.from_numpy(spec_idx),
-                "snr": snr, "gain": gain, "eq": eq, "tanh": tanh, "bandstop": bandstop, "colored": colored,
-                "pitch": [(a, b, _pinned(torch.from_numpy(c))) for a, b, c in getattr(self, "_pitch", [])]}
+        pr = {"n": n, "noise_off": torch.from_numpy(noise_off), "spec_idx": torch.from_numpy(spec_idx),
+              "snr": snr, "gain": gain, "eq": eq, "tanh": tanh, "bandstop": bandstop, "colored": colored,
+              "pitch": [(a, b, _pinned(torch.from_numpy(c))) for a, b, c in getattr(self, "_pitch", [])]}
+        pr["route"] = self.routes(pr)
+        return pr
+
+    def _colored_fold(self) -> bool:
+        """Whether __call__ mixes colored noise in augment_kernel's pass."""
+        return self.sample_rate == 16000 and os.environ.get("HBK_AUG_COLORED_FOLD", "1") != "0"
+
+    def routes(self, pr: Dict[str, Any]) -> np.ndarray:
+        """first_touch_routes over a prepared call's draws (no draw of its own).
+        The clips colored_noise_kernel reads (all coloured ones without the fold,
+        else the group path's leftovers) count as placed first, like the
+        pitch-shift and band-stop clips."""
+        n = pr["n"]
+        placed_first = np.zeros(n, dtype=bool)
+        for _, _, clips in pr.get("pitch") or []:
+            placed_first[clips.numpy()] = True
+        if pr.get("bandstop") is not None:
+            placed_first[pr["bandstop"][0].numpy()] = True
+        if pr.get("colored") is not None:
+            fd, csnr = pr["colored"][0], pr["colored"][1]
+            if self._colored_fold():
+                rows = ReverbPlan.colored_fallback_rows(csnr, fd, self.batch_size,
+                                                        self.plan.colored_group_path(n, self.batch_size))
+                placed_first[rows.numpy()] = True
+            else:
+                placed_first |= ~torch.isnan(csnr).numpy()
+        eq_on = np.zeros(n, dtype=bool)
+        if pr.get("eq") is not None:
+            eq_on[pr["eq"][1].numpy()] = True
+        tanh_on = np.zeros(n, dtype=bool) if pr.get("tanh") is None else ~torch.isnan(pr["tanh"]).numpy()
+        return first_touch_routes(eq_on, tanh_on, placed_first)
 
     def __call__(self, x: torch.Tensor, out: Optional[torch.Tensor] = None,
-                 prepared: Optional[Dict[str, Any]] = None) -> torch.Tensor:
-        """x [n, >= 23040] f32 on the device -> augmented [n, 23040]."""
+                 prepared: Optional[Dict[str, Any]] = None, source: Optional[Dict[int, SourceView]] = None
+                 ) -> torch.Tensor:
+        """x [n, >= 23040] f32 on the device -> augmented [n, 23040]. ``source``
+        (placement on first touch; x is out, in place): per route (ROUTE_EQ,
+        ROUTE_TANH, ROUTE_AUGMENT) the view its kernel reads the clips of
+        prepared["route"] through; the rows of x for those clips are not read."""
         n = x.shape[0]
         pr = self.prepare(n) if prepared is None else prepared
         if pr["n"] != n:
             raise ValueError(f"prepared for {pr['n']} clips, called with {n}")
+        source = source or {}
+        if source and (out is None or out.data_ptr() != x.data_ptr()):
+            raise ValueError("a source view needs the chain in place (out is x)")
         ev = self._tick("", None)
         if pr["eq"] is not None:  # per-clip Compose: EQ, then tanh (augmented.py:79-90), in place on out
             if out is None:
                 out = torch.empty((n, T), dtype=torch.float32, device=x.device)
             if out.data_ptr() != x.data_ptr():
                 out.copy_(x[:, :T])
-            x = seven_band_eq(out, pr["eq"][0], idx=pr["eq"][1])
+            x = seven_band_eq(out, pr["eq"][0], idx=pr["eq"][1], source=source.get(ROUTE_EQ))
             ev = self._tick("eq", ev)
         if pr["tanh"] is not None:  # per-clip Compose, before the batch chain (augmented.py:325-328)
-            x = tanh_distortion(x, pr["tanh"], out=out)
+            x = tanh_distortion(x, pr["tanh"], out=out, source=source.get(ROUTE_TANH))
             out = x
             ev = self._tick("tanh", ev)
         for num, den, clips in pr.get("pitch") or []:  # batch chain: pitch shift first (augmented.py:93-100)
@@ -453,7 +517,7 @@ class BatchAugmenter:
         colored = None
         if pr["colored"] is not None:  # colored noise precedes the gain (augmented.py:107-118)
             fd, csnr, seed = pr["colored"]
-            if self.sample_rate == 16000 and os.environ.get("HBK_AUG_COLORED_FOLD", "1") != "0":
+            if self._colored_fold():
                 colored = (fd, csnr, seed, self.batch_size)  # mixed in augment_kernel's pass
             else:
                 x = self.plan.colored_noise(x, fd, csnr, seed=seed, out=out, sample_rate=self.sample_rate,
@@ -461,7 +525,7 @@ class BatchAugmenter:
                 out = x
                 ev = self._tick("colored", ev)
         y = self.plan.augment(x, self.ring, pr["noise_off"], pr["snr"], self.spectra, pr["spec_idx"],
-                              out=out, gain=pr["gain"], colored=colored)
+                              out=out, gain=pr["gain"], colored=colored, source=source.get(ROUTE_AUGMENT))
         self._tick("mix_reverb", ev)
         return y
 
@@ -718,8 +782,26 @@ class AugmentedAudioGenerator:
         """Device-resident form used by the feature generator: clips [n, S] f32
         on the device (clip i valid in [0, lengths[i])) -> augmented [n, T]."""
         pr = self.prepare_device(clips, lengths) if prepared is None else prepared
-        placed = place_clips(clips, pr["lens"], pr["pre"], self.target_num_samples)  # the chain runs in place
-        return self.augmenter(placed, out=placed, prepared=pr["chain"])
+        T = self.target_num_samples
+        route = pr["chain"].get("route")
+        if route is None or not first_touch_enabled() or T != ReverbPlan.T or not clips.shape[1]:
+            placed = place_clips(clips, pr["lens"], pr["pre"], T)  # the chain runs in place
+            return self.augmenter(placed, out=placed, prepared=pr["chain"])
+        # placement on first touch: place_kernel writes the ROUTE_PLACE clips only; the other
+        # rows are written by their first consumer, which reads the source through the placement
+        n = clips.shape[0]
+        lens = np.asarray(pr["lens"], dtype=np.int32).reshape(n)
+        pre = np.asarray(pr["pre"], dtype=np.int32).reshape(n)
+        if lens.size and (int(lens.min()) < 0 or int(lens.max()) > clips.shape[1] or int(pre.min()) < 0
+                          or int((pre + np.minimum(lens, T)).max()) > T):
+            raise ValueError("lens / pre must place every clip inside [0, T)")
+        routes = (ROUTE_EQ, ROUTE_TANH, ROUTE_AUGMENT)
+        host = np.stack([lens, pre] + [np.where(route == r, pre, -1).astype(np.int32) for r in routes])
+        dev = _pinned(torch.from_numpy(host)).to(clips.device, non_blocking=True)  # one copy: [5, n]
+        self.placed_rows = np.flatnonzero(route == ROUTE_PLACE).astype(np.int32)  # (read by the tests)
+        placed = place_clips(clips, dev[0], dev[1], T, idx=torch.from_numpy(self.placed_rows))
+        source = {r: SourceView(clips, dev[0], dev[2 + i]) for i, r in enumerate(routes)}
+        return self.augmenter(placed, out=placed, prepared=pr["chain"], source=source)
 
     def __call__(self, num_samples: int, **kwargs: Any) -> Iterator[Dict[str, Any]]:
         """augmented.py:396-427: yields {"audio": {"array", "sampling_rate"}, ...}."""

@@ -8,6 +8,7 @@ torch op. Nothing here computes on the CPU.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 import itertools
@@ -776,10 +777,42 @@ def _(src, src_len, pre, T):
     return src.new_empty((src.shape[0], T))
 
 
-def place_clips(src: torch.Tensor, src_len, pre, T: int = 23040) -> torch.Tensor:
+@torch.library.custom_op("hbk::place_clips_idx_", mutates_args=("out",))
+def _place_clips_idx_op(src: torch.Tensor, src_len: torch.Tensor, pre: torch.Tensor, idx: torch.Tensor,
+                        out: torch.Tensor) -> None:
+    check(lib().hbk_place_clips_idx(ptr(src), src.shape[0], src.stride(0), ptr(src_len), ptr(pre), ptr(idx),
+                                    idx.numel(), ptr(out), out.stride(0), out.shape[1], stream_ptr(src.device)),
+          "hbk_place_clips_idx")
+
+
+class SourceView:
+    """Placement on first touch: the source rows a kernel reads clips through
+    instead of reading placed rows. src [n, S] f32 and lens [n] int32 on the
+    device; pre [n] int32 on the device, per consumer: >= 0 reads clip i as
+    place_clips would have placed it with that offset, < 0 reads the placed row."""
+
+    def __init__(self, src: torch.Tensor, lens: torch.Tensor, pre: torch.Tensor) -> None:
+        n = src.shape[0]
+        if src.dim() != 2 or src.dtype != torch.float32 or src.stride(1) != 1:
+            raise ValueError("src must be [n, S] float32 rows on the device")
+        for t in (lens, pre):
+            if t.dtype != torch.int32 or t.shape != (n,) or t.device != src.device or not t.is_contiguous():
+                raise ValueError("lens / pre must be [n] int32 on src's device")
+        self.src, self.lens, self.pre = src, lens, pre
+
+    def check(self, x: torch.Tensor) -> "SourceView":
+        if self.src.shape[0] != x.shape[0] or self.src.device != x.device:
+            raise ValueError("the source view must cover x's clips on x's device")
+        return self
+
+
+def place_clips(src: torch.Tensor, src_len, pre, T: int = 23040, idx: torch.Tensor | None = None,
+                out: torch.Tensor | None = None) -> torch.Tensor:
     """AugmentedAudioGenerator.to_target_length on the device (hbk_place_clips):
     src [n, S] f32 rows holding src_len[i] valid samples -> [n, T] with clip i
-    shifted right by pre[i] zeros and cut at T."""
+    shifted right by pre[i] zeros and cut at T. With ``idx`` (int32 clip rows;
+    hbk_place_clips_idx) only those rows of ``out`` (default: a new, otherwise
+    uninitialised [n, T]) are written; src_len and pre are then device tensors."""
     dev = _native.require_device(src.device)
     if src.dim() != 2 or src.dtype != torch.float32 or src.stride(1) != 1:
         raise ValueError("src must be [n, S] float32 rows on the device")
@@ -800,7 +833,22 @@ def place_clips(src: torch.Tensor, src_len, pre, T: int = 23040) -> torch.Tensor
     elif int(np.max(np.asarray(src_len), initial=0)) > src.shape[1]:
         raise ValueError(f"src_len exceeds the {src.shape[1]} source columns")
     src_len, pre = per_clip(src_len), per_clip(pre)
-    return torch.ops.hbk.place_clips(src, src_len, pre, int(T))
+    if idx is None and out is None:
+        return torch.ops.hbk.place_clips(src, src_len, pre, int(T))
+    if out is None:
+        out = torch.empty((n, int(T)), dtype=torch.float32, device=dev)
+    elif out.shape != (n, int(T)) or out.dtype != torch.float32 or out.stride(1) != 1 or out.device != dev:
+        raise ValueError("out must be [n, T] float32 rows on src's device")
+    if idx is None:
+        idx = torch.arange(n, dtype=torch.int32)
+    idx = idx.to(dtype=torch.int32).reshape(-1).contiguous()
+    if idx.device.type == "cpu":
+        if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= n):
+            raise ValueError("idx out of range")
+        idx = idx.pin_memory().to(dev, non_blocking=True)
+    if idx.numel():
+        torch.ops.hbk.place_clips_idx_(src, src_len, pre, idx, out)
+    return out
 
 
 def _active_rows(values: torch.Tensor) -> torch.Tensor | None:
@@ -811,10 +859,12 @@ def _active_rows(values: torch.Tensor) -> torch.Tensor | None:
     return torch.from_numpy(np.flatnonzero(~np.isnan(values.numpy())).astype(np.int32))
 
 
-def tanh_distortion(x: torch.Tensor, amount: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+def tanh_distortion(x: torch.Tensor, amount: torch.Tensor, out: torch.Tensor | None = None,
+                    source: SourceView | None = None) -> torch.Tensor:
     """audiomentations TanhDistortion per clip on x [n, >= 23040] -> out [n, 23040]
     (hbk_tanh_distortion); amount per clip, NaN leaves the clip unchanged. A
-    host ``amount`` launches over the clips it switches on only."""
+    host ``amount`` launches over the clips it switches on only. ``source``: the
+    clips with source.pre >= 0 (their amount is not NaN) are read through it."""
     T = ReverbPlan.T
     dev = _native.require_device(x.device)
     n = x.shape[0]
@@ -834,7 +884,8 @@ def tanh_distortion(x: torch.Tensor, amount: torch.Tensor, out: torch.Tensor | N
         if rows.numel() == 0:
             return out
         rows = rows.pin_memory().to(dev, non_blocking=True)
-    torch.ops.hbk.tanh_distortion_(x, amount, rows, out)
+    sv = (None, None, None) if source is None else (source.check(x).src, source.lens, source.pre)
+    torch.ops.hbk.tanh_distortion_(x, amount, rows, out, *sv)
     return out
 
 
@@ -889,14 +940,22 @@ def _pitch_shift_op(x: torch.Tensor, idx: torch.Tensor, num: int, den: int, samp
           "hbk_pitch_shift")
 
 
+def _view_args(src: torch.Tensor | None, src_len: torch.Tensor | None, src_pre: torch.Tensor | None) -> tuple:
+    """The four source-view arguments of the hbk_*_src entry points."""
+    if src is None:
+        return None, 0, None, None
+    return ptr(src), src.stride(0), ptr(src_len), ptr(src_pre)
+
+
 def seven_band_eq(x: torch.Tensor, coef: torch.Tensor, out: torch.Tensor | None = None,
-                  idx: torch.Tensor | None = None) -> torch.Tensor:
+                  idx: torch.Tensor | None = None, source: SourceView | None = None) -> torch.Tensor:
     """audiomentations SevenBandParametricEQ per clip (hbk_seven_band_eq).
     Without ``idx``: every clip of x [n, >= 23040] -> out [n, 23040], coef
     [n, 7, 5] float64 (b0, b1, b2, a1, a2 of the low shelf, five peaks and high
     shelf, normalised by a0), a NaN coef[i, 0, 0] copies clip i. With ``idx``
     (int32 [m]): only clips idx[j] with coef [m, 7, 5], written into out
-    (default: in place into x)."""
+    (default: in place into x). ``source``: the listed clips with source.pre >= 0
+    are read through it."""
     T = ReverbPlan.T
     dev = _native.require_device(x.device)
     n = x.shape[0]
@@ -920,22 +979,31 @@ def seven_band_eq(x: torch.Tensor, coef: torch.Tensor, out: torch.Tensor | None 
     elif out is None:
         out = torch.empty((n, T), dtype=torch.float32, device=dev)
     if m:
-        torch.ops.hbk.seven_band_eq_(x, coef, idx, out)
+        sv = (None, None, None) if source is None else (source.check(x).src, source.lens, source.pre)
+        torch.ops.hbk.seven_band_eq_(x, coef, idx, out, *sv)
     return out
 
 
 @torch.library.custom_op("hbk::seven_band_eq_", mutates_args=("out",))
-def _seven_band_eq_op(x: torch.Tensor, coef: torch.Tensor, idx: torch.Tensor | None, out: torch.Tensor) -> None:
-    check(lib().hbk_seven_band_eq(ptr(x), x.shape[0], x.stride(0), ptr(coef), ptr(idx) if idx is not None else None,
-                                  idx.numel() if idx is not None else x.shape[0], ptr(out), out.stride(0),
-                                  stream_ptr(x.device)), "hbk_seven_band_eq")
+def _seven_band_eq_op(x: torch.Tensor, coef: torch.Tensor, idx: torch.Tensor | None, out: torch.Tensor,
+                      src: torch.Tensor | None = None, src_len: torch.Tensor | None = None,
+                      src_pre: torch.Tensor | None = None) -> None:
+    check(lib().hbk_seven_band_eq_src(ptr(x), x.shape[0], x.stride(0), ptr(coef),
+                                      ptr(idx) if idx is not None else None,
+                                      idx.numel() if idx is not None else x.shape[0], ptr(out), out.stride(0),
+                                      *_view_args(src, src_len, src_pre), stream_ptr(x.device)),
+          "hbk_seven_band_eq_src")
 
 
 @torch.library.custom_op("hbk::tanh_distortion_", mutates_args=("out",))
-def _tanh_distortion_op(x: torch.Tensor, amount: torch.Tensor, rows: torch.Tensor | None, out: torch.Tensor) -> None:
-    check(lib().hbk_tanh_distortion(ptr(x), x.shape[0], x.stride(0), ptr(amount),
-                                    ptr(rows) if rows is not None else None, rows.numel() if rows is not None else 0,
-                                    ptr(out), out.stride(0), stream_ptr(x.device)), "hbk_tanh_distortion")
+def _tanh_distortion_op(x: torch.Tensor, amount: torch.Tensor, rows: torch.Tensor | None, out: torch.Tensor,
+                        src: torch.Tensor | None = None, src_len: torch.Tensor | None = None,
+                        src_pre: torch.Tensor | None = None) -> None:
+    check(lib().hbk_tanh_distortion_src(ptr(x), x.shape[0], x.stride(0), ptr(amount),
+                                        ptr(rows) if rows is not None else None,
+                                        rows.numel() if rows is not None else 0, ptr(out), out.stride(0),
+                                        *_view_args(src, src_len, src_pre), stream_ptr(x.device)),
+          "hbk_tanh_distortion_src")
 
 
 BAND_STOP_CIRCULAR_MAX_HALF = 512  # HBK_BAND_STOP_CIRCULAR_MAX_HALF (include/hbk.h)
@@ -993,12 +1061,14 @@ class ReverbPlan:
     def augment(self, x: torch.Tensor, ring: torch.Tensor | None, noise_off: torch.Tensor,
                 snr_db: torch.Tensor, spectra: torch.Tensor | None, spec_idx: torch.Tensor,
                 out: torch.Tensor | None = None, gain: torch.Tensor | None = None,
-                colored: tuple | None = None) -> torch.Tensor:
+                colored: tuple | None = None, source: SourceView | None = None) -> torch.Tensor:
         """x [n, >= T] -> out [n, T]; per clip gain (linear factor, if given), then
         noise (noise_off >= 0), then reverb (spec_idx >= 0). ``colored`` =
         (f_decay, snr_db, seed, clips_per_noise) runs colored_noise() with the
         generated white noise first, in the same pass (hbk_augment_colored:
-        bit-identical to the two calls, each clip read and written once)."""
+        bit-identical to the two calls, each clip read and written once).
+        ``source``: the clips with source.pre >= 0 are read through it; none of
+        them may be among colored_fallback_rows (those are coloured from x first)."""
         n = x.shape[0]
         if x.dim() != 2 or x.shape[1] < self.T or x.stride(1) != 1 or x.device != self.device:
             raise ValueError(f"x must be [n, >= {self.T}] f32 rows on {self.device}")
@@ -1036,8 +1106,9 @@ class ReverbPlan:
         noise_off, spec_idx, snr_db = to_dev(noise_off), to_dev(spec_idx), to_dev(snr_db)
         if gain is not None:
             gain = to_dev(gain)
+        sv = (None, None, None) if source is None else (source.check(x).src, source.lens, source.pre)
         if colored is None:
-            torch.ops.hbk.augment_(x, ring, noise_off, snr_db, spectra, spec_idx, gain, out, self.id)
+            torch.ops.hbk.augment_(x, ring, noise_off, snr_db, spectra, spec_idx, gain, out, self.id, *sv)
             return out
         f_decay, c_snr, seed, clips_per_noise = colored
         f_decay, c_snr = per_clip(f_decay, torch.float32), per_clip(c_snr, torch.float32)
@@ -1053,11 +1124,9 @@ class ReverbPlan:
         # an f_decay other than its group's first clip's): coloured per clip before the pass
         rows = None
         if c_snr.device.type == "cpu" and f_decay.device.type == "cpu":
-            on = ~torch.isnan(c_snr)
-            if ws is not None:
-                first = (torch.arange(n) // clips_per_noise) * clips_per_noise
-                on &= torch.isnan(c_snr[first]) | (f_decay != f_decay[first])
-            rows = torch.nonzero(on).reshape(-1).to(torch.int32)
+            rows = self.colored_fallback_rows(c_snr, f_decay, clips_per_noise, ws is not None)
+        elif source is not None:
+            raise ValueError("a source view needs host c_snr / f_decay (the clips coloured from x are placed)")
         n_rows = -1 if rows is None else rows.numel()  # -1: the kernel scans every clip
         if n_rows == 0:
             rows = torch.zeros(1, dtype=torch.int32)  # a valid pointer with no entries
@@ -1065,16 +1134,33 @@ class ReverbPlan:
             rows = rows.pin_memory().to(self.device, non_blocking=True)
         torch.ops.hbk.augment_colored_(x, ring, noise_off, snr_db, spectra, spec_idx, gain, to_dev(f_decay),
                                        to_dev(c_snr), _u64_to_i64(seed), int(clips_per_noise), rows, n_rows, out,
-                                       ws, self.id)
+                                       ws, self.id, *sv)
         return out
 
-    def _colored_workspace(self, n: int, clips_per_noise: int) -> torch.Tensor | None:
+    @staticmethod
+    def colored_fallback_rows(c_snr: torch.Tensor, f_decay: torch.Tensor, clips_per_noise: int,
+                              group_path: bool) -> torch.Tensor:
+        """int32 rows of the coloured clips (host c_snr not NaN) that the group
+        path does not cover: all of them without it, else those whose group's
+        first clip drew no noise or another f_decay. colored_noise_kernel colours
+        them from x before augment_kernel's pass."""
+        on = ~torch.isnan(c_snr)
+        if group_path:
+            first = (torch.arange(c_snr.numel()) // clips_per_noise) * clips_per_noise
+            on &= torch.isnan(c_snr[first]) | (f_decay != f_decay[first])
+        return torch.nonzero(on).reshape(-1).to(torch.int32)
+
+    def colored_group_path(self, n: int, clips_per_noise: int) -> bool:
+        """Whether augment(colored=...) over n clips takes the group path
+        (_colored_workspace's conditions, without allocating)."""
         ws_bytes = int(lib().hbk_colored_noise_workspace_size(n, int(clips_per_noise)))
-        if (os.environ.get("HBK_COLORED_NO_GROUP") or ws_bytes > (1 << 30)
-                or int(clips_per_noise) < self.COLORED_GROUP_MIN):
+        return not (os.environ.get("HBK_COLORED_NO_GROUP") or ws_bytes > (1 << 30)
+                    or int(clips_per_noise) < self.COLORED_GROUP_MIN or ws_bytes <= 0)
+
+    def _colored_workspace(self, n: int, clips_per_noise: int) -> torch.Tensor | None:
+        if not self.colored_group_path(n, clips_per_noise):
             return None  # A/B switch; small groups are not worth 64 KB of resident workspace each
-        if ws_bytes <= 0:
-            return None
+        ws_bytes = int(lib().hbk_colored_noise_workspace_size(n, int(clips_per_noise)))
         ws = self._cn_ws
         if ws is None or ws.numel() < ws_bytes:
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
@@ -1193,15 +1279,33 @@ def _reverb_spectrum_op(kernels: torch.Tensor, out: torch.Tensor, plan_id: int) 
                                     stream_ptr(kernels.device)), "hbk_reverb_spectrum")
 
 
+@contextlib.contextmanager
+def _plan_source(plan: "ReverbPlan", src: torch.Tensor | None, src_len: torch.Tensor | None,
+                 src_pre: torch.Tensor | None):
+    """The plan's source view (hbk_reverb_plan_set_source) for the launches inside."""
+    if src is None:
+        yield
+        return
+    check(lib().hbk_reverb_plan_set_source(plan._handle, *_view_args(src, src_len, src_pre)),
+          "hbk_reverb_plan_set_source")
+    try:
+        yield
+    finally:
+        lib().hbk_reverb_plan_set_source(plan._handle, None, 0, None, None)
+
+
 @torch.library.custom_op("hbk::augment_", mutates_args=("out",))
 def _augment_op(x: torch.Tensor, ring: torch.Tensor | None, noise_off: torch.Tensor, snr_db: torch.Tensor,
                 spectra: torch.Tensor | None, spec_idx: torch.Tensor, gain: torch.Tensor | None, out: torch.Tensor,
-                plan_id: int) -> None:
+                plan_id: int, src: torch.Tensor | None = None, src_len: torch.Tensor | None = None,
+                src_pre: torch.Tensor | None = None) -> None:
     plan = _plans[plan_id]
     opt = lambda t: ptr(t) if t is not None else None  # noqa: E731
-    check(lib().hbk_augment(plan._handle, ptr(x), x.shape[0], x.stride(0), opt(ring),
-                            0 if ring is None else ring.numel(), ptr(noise_off), ptr(snr_db), opt(spectra),
-                            ptr(spec_idx), opt(gain), ptr(out), out.stride(0), stream_ptr(x.device)), "hbk_augment")
+    with _plan_source(plan, src, src_len, src_pre):
+        check(lib().hbk_augment(plan._handle, ptr(x), x.shape[0], x.stride(0), opt(ring),
+                                0 if ring is None else ring.numel(), ptr(noise_off), ptr(snr_db), opt(spectra),
+                                ptr(spec_idx), opt(gain), ptr(out), out.stride(0), stream_ptr(x.device)),
+              "hbk_augment")
 
 
 @torch.library.custom_op("hbk::augment_colored_", mutates_args=("out", "workspace"))
@@ -1209,16 +1313,18 @@ def _augment_colored_op(x: torch.Tensor, ring: torch.Tensor | None, noise_off: t
                         spectra: torch.Tensor | None, spec_idx: torch.Tensor, gain: torch.Tensor | None,
                         f_decay: torch.Tensor, c_snr: torch.Tensor, seed: int, clips_per_noise: int,
                         rows: torch.Tensor | None, n_rows: int, out: torch.Tensor, workspace: torch.Tensor | None,
-                        plan_id: int) -> None:
+                        plan_id: int, src: torch.Tensor | None = None, src_len: torch.Tensor | None = None,
+                        src_pre: torch.Tensor | None = None) -> None:
     plan = _plans[plan_id]
     opt = lambda t: ptr(t) if t is not None else None  # noqa: E731
-    check(lib().hbk_augment_colored(plan._handle, ptr(x), x.shape[0], x.stride(0), opt(ring),
-                                    0 if ring is None else ring.numel(), ptr(noise_off), ptr(snr_db), opt(spectra),
-                                    ptr(spec_idx), opt(gain), None, 0, seed & (2 ** 64 - 1), clips_per_noise,
-                                    ptr(f_decay), ptr(c_snr), 16000.0, opt(rows) if n_rows >= 0 else None,
-                                    max(n_rows, 0), ptr(out), out.stride(0),
-                                    opt(workspace), workspace.numel() if workspace is not None else 0,
-                                    stream_ptr(x.device)), "hbk_augment_colored")
+    with _plan_source(plan, src, src_len, src_pre):
+        check(lib().hbk_augment_colored(plan._handle, ptr(x), x.shape[0], x.stride(0), opt(ring),
+                                        0 if ring is None else ring.numel(), ptr(noise_off), ptr(snr_db),
+                                        opt(spectra), ptr(spec_idx), opt(gain), None, 0, seed & (2 ** 64 - 1),
+                                        clips_per_noise, ptr(f_decay), ptr(c_snr), 16000.0,
+                                        opt(rows) if n_rows >= 0 else None, max(n_rows, 0), ptr(out), out.stride(0),
+                                        opt(workspace), workspace.numel() if workspace is not None else 0,
+                                        stream_ptr(x.device)), "hbk_augment_colored")
 
 
 @torch.library.custom_op("hbk::colored_noise_", mutates_args=("out", "workspace"))

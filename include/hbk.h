@@ -583,6 +583,34 @@ int hbk_tanh_distortion(const float* x, int64_t n_clips, int64_t x_stride, const
  * T % 4 == 0, out rows 16-B aligned. One persistent launch (4,096-sample spans of the clips). */
 int hbk_place_clips(const float* src, int64_t n_clips, int64_t src_stride, const int32_t* src_len,
                     const int32_t* pre, float* out, int64_t out_stride, int64_t T, void* stream);
+/* The same for the n_entries clip rows idx lists only (idx NULL: every row, as
+ * hbk_place_clips); the other rows of out are not written. */
+int hbk_place_clips_idx(const float* src, int64_t n_clips, int64_t src_stride, const int32_t* src_len,
+                        const int32_t* pre, const int32_t* idx, int64_t n_entries, float* out,
+                        int64_t out_stride, int64_t T, void* stream);
+
+/* Placement on first touch: a clip's first consumer can read the source row
+ * through the placement instead of reading a placed row, so that
+ * hbk_place_clips_idx writes only the clips no such kernel reads first. The
+ * source view is src [n_clips, src_stride], src_len[i] valid samples, and
+ * src_pre[i]: >= 0 reads clip i as hbk_place_clips would have placed it with
+ * pre = src_pre[i] and T = 23040 (the same loads, so the same bits), < 0 reads
+ * x[i] as without a view. All three NULL: no view. hbk_seven_band_eq_src and
+ * hbk_tanh_distortion_src are hbk_seven_band_eq and hbk_tanh_distortion with a
+ * view (a clip read through it must be listed / have a non-NaN amount);
+ * hbk_reverb_plan_set_source sets the view of the plan's following hbk_augment
+ * and hbk_augment_colored launches (all NULL clears it); a clip that
+ * hbk_augment_colored's c_idx lists must have src_pre < 0. */
+int hbk_seven_band_eq_src(const float* x, int64_t n_clips, int64_t x_stride, const double* coef,
+                          const int32_t* idx, int64_t n_entries, float* out, int64_t out_stride,
+                          const float* src, int64_t src_stride, const int32_t* src_len,
+                          const int32_t* src_pre, void* stream);
+int hbk_tanh_distortion_src(const float* x, int64_t n_clips, int64_t x_stride, const float* amount,
+                            const int32_t* idx, int64_t n_entries, float* out, int64_t out_stride,
+                            const float* src, int64_t src_stride, const int32_t* src_len,
+                            const int32_t* src_pre, void* stream);
+int hbk_reverb_plan_set_source(hbk_reverb_plan* plan, const float* src, int64_t src_stride,
+                               const int32_t* src_len, const int32_t* src_pre);
 
 #ifdef __cplusplus
 }
