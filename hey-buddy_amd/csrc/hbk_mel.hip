@@ -16,26 +16,20 @@
 //   products (each filter's non-zero bins are contiguous), 10 log10, /10 + 2.
 // The 4 frames of a wave only exchange data through the wave's own LDS slice,
 // so no workgroup barrier is needed after the table load.
-#include <algorithm>
-#include <cmath>
+//
+// The sizes the kernels and the host share, the routing rule, the tables and the
+// launch grids are in hbk_mel_plan.h (plain C++, run on the CPU by its own test).
 #include <cstdlib>
-#include <vector>
+#include <type_traits>
 
 #include "hbk_common.h"
+#include "hbk_mel_plan.h"
 
 namespace hbk {
 namespace {
 
-constexpr int kNfft = 512;
-constexpr int kFramesPerWave = 4;
-constexpr int kWaves = 4;
-constexpr int kThreads = 64 * kWaves;
-constexpr int kFramesPerBlock = kFramesPerWave * kWaves;
 constexpr int kRow = 17;                  // transpose row: 16 complex + 1 pad (bank spread)
 constexpr int kFrameC = 16 * kRow + 1;    // 273 complex = 2184 B per frame (== 8 mod 16 B)
-constexpr int kMaxTaps = 16;              // widest mel filter supported
-constexpr int kMaxMels = 32;
-constexpr int kBlocksPerCU = 8;           // persistent grid: CUs x this
 
 struct MelArgs {
   const float* pcm;
@@ -321,13 +315,6 @@ __global__ void __launch_bounds__(kThreads) mel_frames_kernel(MelArgs a) {
 //    exact in binary floating point).
 constexpr int kRow2 = 18;
 constexpr int kFrameC2 = 16 * kRow2;  // 288 complex = 2304 B
-constexpr int kTapsA = 8;             // filters 0..15
-constexpr int kTapsB = 16;            // filters 16..31
-constexpr int kBins2 = 128;
-constexpr int kWaves2 = 8;            // 512-thread blocks sharing one constant table
-constexpr int kThreads2 = 64 * kWaves2;
-constexpr int kFramesPerBlock2 = kFramesPerWave * kWaves2;
-constexpr int kBlocksPerCU2 = 2;      // <= 128 VGPRs, 80 KB LDS: 4 waves / SIMD
 
 struct Mel2Args {
   const float* pcm;
@@ -536,10 +523,6 @@ mel_frames_v2_kernel(Mel2Args a) {
 //    (n, kq), i.e. the log of v2's 2 values per lane;
 //  - 6-wave blocks (2 per CU: the split weight planes take 17 KB of LDS).
 // The dense product multiplies ~4x the non-zero taps, on the matrix pipe.
-constexpr int kWaves3 = 6;
-constexpr int kThreads3 = 64 * kWaves3;
-constexpr int kFramesPerBlock3 = kFramesPerWave * kWaves3;
-constexpr int kBlocksPerCU3 = 2;
 constexpr int kWLd3 = kBins2 + 8;  // bf16 per mel row of a weight plane (bank spread)
 typedef __bf16 h8m __attribute__((ext_vector_type(8)));
 typedef __bf16 h2m __attribute__((ext_vector_type(2)));
@@ -775,15 +758,7 @@ mel_frames_mfma_kernel(Mel3Args a) {
 // stage-B reads (24 f + 17 jj + n2) and the power stores are conflict-free
 // (tools/lds_bank_sim.py; the first 577-dword layout ran the stores 4-way). The power
 // row sits at +24 (f & 1) + 8 (f >> 1 & 1) (8-B aligned pairs for the filter reads).
-constexpr int kFramesPerWave4 = 8;
-constexpr int kLdt4 = 17, kFs4 = 280;
-constexpr int kBlocksPerCU4 = 3;  // 3 x (35 KB frames + 6.5 KB table) of LDS, <= 168 VGPRs
-// constant table [entry][8 lanes] of float4
-constexpr int kE4Win = 0;           // 16: (w[32 n1 + 2jj], w[.. + 16], w[.. + 1], w[.. + 17])
-constexpr int kE4Tw = 16;           // 16 (k1 = 0 unused): (Re W^(jj k1), Re W^((jj+8) k1), Im .., Im ..)
-constexpr int kE4Ws = 32;           // 8: -i W512^k for bins (ra + 16 k2, rb + 16 k2), re pair, im pair
-constexpr int kE4Mel = 40;          // 12: weights of A slots jj, jj + 8 (8 each), B slots jj, jj + 8 (16 each)
-constexpr int kE4N = 52;
+constexpr int kLdt4 = 17, kFs4 = 280;  // (the constant table [kE4N][8 lanes] of float4: hbk_mel_plan.h)
 
 struct P2 {
   cf r, i;
@@ -1022,35 +997,80 @@ mel_frames_soa_kernel(Mel4Args a) {
 #define HBK_MEL_V3(e) (hbk::mel_frames_mfma_kernel<e, hbk::sc>)
 #endif
 
+static_assert(hbk::kPlanOk == HBK_OK && hbk::kPlanErrArg == HBK_ERR_ARG && hbk::kPlanErrUnsupported == HBK_ERR_UNSUPPORTED,
+              "hbk_mel_plan.h returns hbk_status values");
+
 struct hbk_mel_plan {
-  int n_fft, hop, n_mels, taps, nk2, need256;
+  int n_fft, hop, n_mels;
   float log_floor, out_div, out_add;
-  float* d_window = nullptr;
-  float2* d_tw256 = nullptr;
-  float2* d_tw512 = nullptr;
-  int* d_lo = nullptr;
-  float* d_w = nullptr;
-  // v2 (32 mels, bins < 128): -i W512^k, even start bins, x 1/4 weights
-  int v2 = 0, edge0 = 0;
-  float2* d_twsm = nullptr;
-  int* d_lo2 = nullptr;
-  float* d_w2 = nullptr;
-  // v3 (hbk_mel_set_variant 1): the dense filterbank^T [32][128] x 1/4 for the MFMA variant
-  int variant = 0;
-  float* d_fbt = nullptr;
-  // v4 (HBK_MEL_V4): 4 or 8 waves per block, 0 = v2; its per-lane constant table
-  int v4 = 0;
-  float4* d_t4 = nullptr;
+  hbk::MelScalars s;  // s.variant: hbk_mel_set_variant
+  // hbk::MelTables::host on the device, and where its tables start
+  char* d_tables = nullptr;
+  size_t off[hbk::kMelTableCount] = {};
+  template <class T>
+  const T* table(hbk::MelTable t) const { return reinterpret_cast<const T*>(d_tables + off[t]); }
 };
 
-// The kernel hbk_mel_frames launches for a plan (hbk_mel_plan_info's numbering):
-// 1 = v1, 2 = v2, 3 = MFMA, 4 / 8 = SoA with 4 / 8 waves per block.
-static int mel_route(const hbk_mel_plan* plan) {
-  if (!plan->v2) return 1;
-  if (plan->variant == 1) return 3;
-  if (plan->v4) return plan->v4 == 8 ? 8 : 4;
-  return 2;
+namespace hbk {
+namespace {
+
+// The unit's environment, read once per hbk_mel_plan_create. HBK_MEL_V1 / HBK_MEL_MFMA: set or not;
+// HBK_MEL_V4: 0 or unset off (as the other HBK_* knobs read their values), 8 -> 8-wave blocks, else 4-wave.
+MelKnobs read_mel_knobs() {
+  MelKnobs k;
+  k.force_v1 = getenv("HBK_MEL_V1") != nullptr;
+  k.mfma = getenv("HBK_MEL_MFMA") != nullptr;
+  const char* v4 = getenv("HBK_MEL_V4");
+  const int v4n = v4 ? atoi(v4) : 0;
+  k.v4 = v4n == 0 ? 0 : (v4n == 8 ? 8 : 4);
+  return k;
 }
+
+// each route's kernel, [edge0] (v1 has one form; its plans have edge0 = 0)
+void (*const kMelV1[2])(MelArgs) = {mel_frames_kernel, mel_frames_kernel};
+void (*const kMelV2[2])(Mel2Args) = {HBK_MEL_V2(false), HBK_MEL_V2(true)};
+void (*const kMelMfma[2])(Mel3Args) = {HBK_MEL_V3(false), HBK_MEL_V3(true)};
+template <int W>
+void (*const kMelSoa[2])(Mel4Args) = {mel_frames_soa_kernel<false, W>, mel_frames_soa_kernel<true, W>};
+
+struct MelCall {
+  const hbk_mel_plan* plan;
+  const float* pcm;
+  float* out;
+  int64_t n_clips, clip_stride, n_frames;
+  void* stream;
+  MelLaunch grid;
+};
+
+// Fills the fields every argument struct has (the caller set the route's tables) and launches kernel[edge0].
+template <class Args>
+int mel_run(const MelCall& c, Args a, void (*const (&kernel)[2])(Args), const char* name) {
+  const hbk_mel_plan* p = c.plan;
+  a.pcm = c.pcm;
+  a.out = c.out;
+  a.n_clips = c.n_clips;
+  a.clip_stride = c.clip_stride;
+  a.n_frames = c.n_frames;
+  a.hop = p->hop;
+  a.log_floor = p->log_floor;
+  if constexpr (std::is_same_v<Args, MelArgs>)
+    a.out_div = p->out_div;
+  else
+    a.out_scale = 10.f / p->out_div;
+  a.out_add = p->out_add;
+  hipLaunchKernelGGL(kernel[p->s.edge0], dim3(static_cast<unsigned>(c.grid.blocks)), dim3(c.grid.threads), 0,
+                     as_stream(c.stream), a);
+  HBK_LAUNCH_CHECK(name);
+  return HBK_OK;
+}
+
+int plan_error(int rc, const std::string& err) {
+  set_error("%s", err.c_str());
+  return rc;
+}
+
+}  // namespace
+}  // namespace hbk
 
 extern "C" {
 
@@ -1060,166 +1080,30 @@ int hbk_mel_plan_create(const float* window, const float* fbank, int n_fft, int 
   using namespace hbk;
   if (!plan) return arg_error("plan is NULL");
   *plan = nullptr;
-  if (!window || !fbank) return arg_error("window/fbank is NULL");
-  if (n_fft != kNfft) return arg_error("n_fft must be 512");
-  if (hop <= 0) return arg_error("hop must be positive");
-  if (n_mels <= 0 || n_mels > kMaxMels || (n_mels & 1)) return arg_error("n_mels must be even and <= 32");
-  if (out_div == 0.f) return arg_error("out_div must be non-zero");
-  const int n_freq = n_fft / 2 + 1;
-
-  // Sparse filterbank: each filter's non-zero bins form one contiguous run.
-  std::vector<int> lo(n_mels, 0), hi(n_mels, -1);
-  int taps = 1;
-  for (int m = 0; m < n_mels; ++m) {
-    for (int k = 0; k < n_freq; ++k) {
-      if (fbank[k * n_mels + m] != 0.f) {
-        if (hi[m] < 0) lo[m] = k;
-        hi[m] = k;
-      }
-    }
-    if (hi[m] < 0) { lo[m] = 0; hi[m] = 0; }  // all-zero filter: weights stay 0
-    taps = std::max(taps, hi[m] - lo[m] + 1);
-  }
-  // v2 layout: 32 mels reading bins < 128 only. Lane j computes filter j from
-  // kTapsA bins and filter 31 - j from kTapsB bins, each from an even start
-  // (8-B LDS pairs) kept inside [0, 128); weights x 1/4, zero outside the filter.
-  int kmax_all = 0;
-  for (int m = 0; m < n_mels; ++m) kmax_all = std::max(kmax_all, hi[m]);
-  bool v2 = n_mels == kMaxMels && kmax_all < kBins2 && !getenv("HBK_MEL_V1");
-  std::vector<int> lo2(kMaxMels, 0);
-  std::vector<float> w2(16 * (kTapsA + kTapsB), 0.f);
-  for (int m = 0; v2 && m < n_mels; ++m) {
-    const int T = m < 16 ? kTapsA : kTapsB;
-    int l = lo[m] & ~1;
-    if (hi[m] - l + 1 > T) {
-      v2 = false;
-      break;
-    }
-    if (l + T > kBins2) l = kBins2 - T;  // even: T is even
-    const int slot_j = m < 16 ? m : 31 - m;
-    lo2[m < 16 ? slot_j : 16 + slot_j] = l;
-    float* w = w2.data() + (m < 16 ? slot_j * kTapsA : 16 * kTapsA + slot_j * kTapsB);
-    for (int t = 0; t < T; ++t) w[t] = 0.25f * fbank[(l + t) * n_mels + m];
-  }
-  bool edge0 = true;
-  for (int i = 0; i < 32; ++i) edge0 = edge0 && window[i] == 0.f && window[n_fft - 1 - i] == 0.f;
-  if (taps > kMaxTaps) {
-    set_error("hbk: mel filter spans %d bins (> %d supported)", taps, kMaxTaps);
-    return HBK_ERR_UNSUPPORTED;
-  }
-  std::vector<float> w(static_cast<size_t>(n_mels) * taps, 0.f);
-  int kmax = 0;
-  for (int m = 0; m < n_mels; ++m) {
-    if (lo[m] + taps > n_freq) lo[m] = n_freq - taps;  // keep reads inside [0, 257)
-    for (int t = 0; t < taps; ++t) w[m * taps + t] = fbank[(lo[m] + t) * n_mels + m];
-    kmax = std::max(kmax, lo[m] + taps - 1);
-  }
-  const int need256 = kmax >= 256 ? 1 : 0;
-  const int nk2 = std::min(16, (std::min(kmax, 255) + 16) / 16);
-
-  std::vector<float> win(n_fft);
-  for (int i = 0; i < n_fft; ++i) win[i] = window[i] * in_scale;
-  std::vector<float2> tw256(256), tw512(257);
-  for (int i = 0; i < 256; ++i) {
-    const double ang = -2.0 * M_PI * i / 256.0;
-    tw256[i] = make_float2(static_cast<float>(cos(ang)), static_cast<float>(sin(ang)));
-  }
-  for (int i = 0; i < 257; ++i) {
-    const double ang = -2.0 * M_PI * i / 512.0;
-    tw512[i] = make_float2(static_cast<float>(cos(ang)), static_cast<float>(sin(ang)));
-  }
+  MelTables t;
+  std::string err;
+  const int rc = mel_tables(window, fbank, n_fft, hop, n_mels, in_scale, log_floor, out_div, out_add,
+                            read_mel_knobs(), t, err);
+  if (rc != kPlanOk) return plan_error(rc, err);
 
   hbk_mel_plan* p = new hbk_mel_plan();
   p->n_fft = n_fft;
   p->hop = hop;
   p->n_mels = n_mels;
-  p->taps = taps;
-  p->nk2 = nk2;
-  p->need256 = need256;
   p->log_floor = log_floor;
   p->out_div = out_div;
   p->out_add = out_add;
-  auto fail = [&](hipError_t e, const char* where) {
+  p->s = t.s;
+  std::copy(t.off, t.off + kMelTableCount, p->off);
+  const char* where = "hipMalloc mel tables";
+  hipError_t e = hipMalloc(&p->d_tables, t.bytes());
+  if (e == hipSuccess) {
+    where = "copy mel tables";
+    e = hipMemcpy(p->d_tables, t.host.data(), t.bytes(), hipMemcpyHostToDevice);
+  }
+  if (e != hipSuccess) {
     hbk_mel_plan_destroy(p);
     return hip_error(e, where);
-  };
-  hipError_t e;
-  if ((e = hipMalloc(&p->d_window, n_fft * sizeof(float))) != hipSuccess) return fail(e, "hipMalloc window");
-  if ((e = hipMalloc(&p->d_tw256, 256 * sizeof(float2))) != hipSuccess) return fail(e, "hipMalloc tw256");
-  if ((e = hipMalloc(&p->d_tw512, 257 * sizeof(float2))) != hipSuccess) return fail(e, "hipMalloc tw512");
-  if ((e = hipMalloc(&p->d_lo, n_mels * sizeof(int))) != hipSuccess) return fail(e, "hipMalloc lo");
-  if ((e = hipMalloc(&p->d_w, w.size() * sizeof(float))) != hipSuccess) return fail(e, "hipMalloc w");
-  if ((e = hipMemcpy(p->d_window, win.data(), n_fft * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess)
-    return fail(e, "copy window");
-  if ((e = hipMemcpy(p->d_tw256, tw256.data(), 256 * sizeof(float2), hipMemcpyHostToDevice)) != hipSuccess)
-    return fail(e, "copy tw256");
-  if ((e = hipMemcpy(p->d_tw512, tw512.data(), 257 * sizeof(float2), hipMemcpyHostToDevice)) != hipSuccess)
-    return fail(e, "copy tw512");
-  if ((e = hipMemcpy(p->d_lo, lo.data(), n_mels * sizeof(int), hipMemcpyHostToDevice)) != hipSuccess)
-    return fail(e, "copy lo");
-  if ((e = hipMemcpy(p->d_w, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess)
-    return fail(e, "copy w");
-  if (v2) {
-    std::vector<float2> twsm(kBins2);
-    for (int k = 0; k < kBins2; ++k) {  // -i W512^k = (sin(-2 pi k/512), -cos(-2 pi k/512))
-      const double ang = -2.0 * M_PI * k / 512.0;
-      twsm[k] = make_float2(static_cast<float>(sin(ang)), static_cast<float>(-cos(ang)));
-    }
-    p->v2 = 1;
-    p->edge0 = edge0 ? 1 : 0;
-    if ((e = hipMalloc(&p->d_twsm, kBins2 * sizeof(float2))) != hipSuccess) return fail(e, "hipMalloc twsm");
-    if ((e = hipMalloc(&p->d_lo2, kMaxMels * sizeof(int))) != hipSuccess) return fail(e, "hipMalloc lo2");
-    if ((e = hipMalloc(&p->d_w2, w2.size() * sizeof(float))) != hipSuccess) return fail(e, "hipMalloc w2");
-    if ((e = hipMemcpy(p->d_twsm, twsm.data(), kBins2 * sizeof(float2), hipMemcpyHostToDevice)) != hipSuccess)
-      return fail(e, "copy twsm");
-    if ((e = hipMemcpy(p->d_lo2, lo2.data(), kMaxMels * sizeof(int), hipMemcpyHostToDevice)) != hipSuccess)
-      return fail(e, "copy lo2");
-    if ((e = hipMemcpy(p->d_w2, w2.data(), w2.size() * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess)
-      return fail(e, "copy w2");
-    std::vector<float> fbt(static_cast<size_t>(kMaxMels) * kBins2);
-    for (int m = 0; m < kMaxMels; ++m)
-      for (int k = 0; k < kBins2; ++k) fbt[m * kBins2 + k] = 0.25f * fbank[k * n_mels + m];
-    if ((e = hipMalloc(&p->d_fbt, fbt.size() * sizeof(float))) != hipSuccess) return fail(e, "hipMalloc fbt");
-    if ((e = hipMemcpy(p->d_fbt, fbt.data(), fbt.size() * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess)
-      return fail(e, "copy fbt");
-    p->variant = getenv("HBK_MEL_MFMA") ? 1 : 0;
-    // v4 table [entry][lane jj]: window, W256 twiddles, split twiddles, filter weights
-    std::vector<float4> t4(static_cast<size_t>(kE4N) * 8, make_float4(0.f, 0.f, 0.f, 0.f));
-    auto W = [](double num) {
-      const double ang = -2.0 * M_PI * num;
-      return std::pair<float, float>(static_cast<float>(cos(ang)), static_cast<float>(sin(ang)));
-    };
-    for (int jj = 0; jj < 8; ++jj) {
-      for (int n1 = 0; n1 < 16; ++n1) {
-        const int s = 32 * n1 + 2 * jj;
-        t4[(kE4Win + n1) * 8 + jj] = make_float4(win[s], win[s + 16], win[s + 1], win[s + 17]);
-      }
-      for (int k1 = 1; k1 < 16; ++k1) {
-        const auto a0 = W(double(jj * k1) / 256.0), a1 = W(double((jj + 8) * k1) / 256.0);
-        t4[(kE4Tw + k1) * 8 + jj] = make_float4(a0.first, a1.first, a0.second, a1.second);
-      }
-      const int ra = jj == 0 ? 0 : jj, rb = jj == 0 ? 8 : 16 - jj;
-      for (int k2 = 0; k2 < 8; ++k2) {
-        const float2 s0 = twsm[ra + 16 * k2], s1 = twsm[rb + 16 * k2];
-        t4[(kE4Ws + k2) * 8 + jj] = make_float4(s0.x, s1.x, s0.y, s1.y);
-      }
-      const float* wa0 = w2.data() + jj * kTapsA;
-      const float* wa1 = w2.data() + (jj + 8) * kTapsA;
-      const float* wb0 = w2.data() + 16 * kTapsA + jj * kTapsB;
-      const float* wb1 = w2.data() + 16 * kTapsA + (jj + 8) * kTapsB;
-      for (int q = 0; q < 2; ++q) t4[(kE4Mel + q) * 8 + jj] = make_float4(wa0[4 * q], wa0[4 * q + 1], wa0[4 * q + 2], wa0[4 * q + 3]);
-      for (int q = 0; q < 2; ++q) t4[(kE4Mel + 2 + q) * 8 + jj] = make_float4(wa1[4 * q], wa1[4 * q + 1], wa1[4 * q + 2], wa1[4 * q + 3]);
-      for (int q = 0; q < 4; ++q) t4[(kE4Mel + 4 + q) * 8 + jj] = make_float4(wb0[4 * q], wb0[4 * q + 1], wb0[4 * q + 2], wb0[4 * q + 3]);
-      for (int q = 0; q < 4; ++q) t4[(kE4Mel + 8 + q) * 8 + jj] = make_float4(wb1[4 * q], wb1[4 * q + 1], wb1[4 * q + 2], wb1[4 * q + 3]);
-    }
-    if ((e = hipMalloc(&p->d_t4, t4.size() * sizeof(float4))) != hipSuccess) return fail(e, "hipMalloc t4");
-    if ((e = hipMemcpy(p->d_t4, t4.data(), t4.size() * sizeof(float4), hipMemcpyHostToDevice)) != hipSuccess)
-      return fail(e, "copy t4");
-    // opt-in until measured on the GPU: HBK_MEL_V4=1 (4-wave blocks, prefetch) or 8 (8-wave blocks)
-    // (0 or unset: off, as the other HBK_* knobs read their values)
-    const char* v4 = getenv("HBK_MEL_V4");
-    const int v4n = v4 ? atoi(v4) : 0;
-    p->v4 = v4n == 0 ? 0 : (v4n == 8 ? 8 : 4);
   }
   *plan = p;
   return HBK_OK;
@@ -1227,16 +1111,7 @@ int hbk_mel_plan_create(const float* window, const float* fbank, int n_fft, int 
 
 int hbk_mel_plan_destroy(hbk_mel_plan* p) {
   if (!p) return HBK_OK;
-  (void)hipFree(p->d_window);
-  (void)hipFree(p->d_tw256);
-  (void)hipFree(p->d_tw512);
-  (void)hipFree(p->d_lo);
-  (void)hipFree(p->d_w);
-  (void)hipFree(p->d_twsm);
-  (void)hipFree(p->d_lo2);
-  (void)hipFree(p->d_w2);
-  (void)hipFree(p->d_fbt);
-  (void)hipFree(p->d_t4);
+  (void)hipFree(p->d_tables);
   delete p;
   return HBK_OK;
 }
@@ -1245,22 +1120,22 @@ int hbk_mel_set_variant(hbk_mel_plan* plan, int32_t variant) {
   using namespace hbk;
   if (!plan) return arg_error("plan is NULL");
   if (variant != 0 && variant != 1) return arg_error("variant must be 0 (sparse VALU) or 1 (MFMA)");
-  if (variant == 1 && !plan->v2) {
+  if (variant == 1 && !plan->s.v2) {
     set_error("hbk: the MFMA filterbank variant covers 32 mels on bins < 128");
     return HBK_ERR_UNSUPPORTED;
   }
-  plan->variant = variant;
+  plan->s.variant = variant;
   return HBK_OK;
 }
 
 int hbk_mel_plan_info(const hbk_mel_plan* plan, int32_t info[8]) {
   using namespace hbk;
   if (!plan || !info) return arg_error("plan/info is NULL");
-  info[0] = mel_route(plan);
-  info[1] = plan->edge0;
-  info[2] = plan->taps;
-  info[3] = plan->nk2;
-  info[4] = plan->need256;
+  info[0] = mel_route(plan->s, plan->s.variant);
+  info[1] = plan->s.edge0;
+  info[2] = plan->s.taps;
+  info[3] = plan->s.nk2;
+  info[4] = plan->s.need256;
   info[5] = plan->n_mels;
   info[6] = info[7] = 0;
   return HBK_OK;
@@ -1270,126 +1145,54 @@ int hbk_mel_frames(const hbk_mel_plan* plan, const float* pcm, int64_t n_clips, 
                    int64_t n_frames, float* out, void* stream) {
   using namespace hbk;
   if (!plan) return arg_error("plan is NULL");
-  if (n_clips < 0 || n_frames < 0) return arg_error("negative size");
-  if (n_clips == 0 || n_frames == 0) return HBK_OK;
-  if (!pcm || !out) return arg_error("pcm/out is NULL");
-  if ((clip_stride & 1) || (plan->hop & 1)) return arg_error("clip_stride and hop must be even (float2 loads)");
-  if ((reinterpret_cast<uintptr_t>(pcm) & 7) || (reinterpret_cast<uintptr_t>(out) & 7))
-    return arg_error("pcm/out must be 8-byte aligned");
-  if (plan->hop * (n_frames - 1) + plan->n_fft > clip_stride) return arg_error("frames exceed clip_stride");
-  const int64_t total = n_clips * n_frames;
-  if (total >= (int64_t(1) << 31)) return arg_error("more than 2^31 frames in one call");
-  const int route = mel_route(plan);
-  if (route == 3) {
-    const int64_t groups3 = (total + kFramesPerBlock3 - 1) / kFramesPerBlock3;
-    Mel3Args a;
-    a.pcm = pcm;
-    a.out = out;
-    a.window = plan->d_window;
-    a.tw256 = plan->d_tw256;
-    a.twsm = plan->d_twsm;
-    a.fbt = plan->d_fbt;
-    a.n_clips = n_clips;
-    a.clip_stride = clip_stride;
-    a.n_frames = n_frames;
-    a.hop = plan->hop;
-    a.log_floor = plan->log_floor;
-    a.out_scale = 10.f / plan->out_div;
-    a.out_add = plan->out_add;
-    const int64_t blocks = std::min<int64_t>(groups3, persistent_blocks(kBlocksPerCU3, stream));
-    if (plan->edge0)
-      hipLaunchKernelGGL(HBK_MEL_V3(true), dim3(static_cast<unsigned>(blocks)), dim3(kThreads3), 0,
-                         as_stream(stream), a);
-    else
-      hipLaunchKernelGGL(HBK_MEL_V3(false), dim3(static_cast<unsigned>(blocks)), dim3(kThreads3), 0,
-                         as_stream(stream), a);
-    HBK_LAUNCH_CHECK("mel_frames_mfma_kernel");
-    return HBK_OK;
-  }
-  if (route == 4 || route == 8) {
-    const int W = route;  // waves per block (hbk_mel_plan::v4)
-    const int64_t fpb = kFramesPerWave4 * W;
-    const int64_t groups4 = (total + fpb - 1) / fpb;
-    Mel4Args a;
-    a.pcm = pcm;
-    a.out = out;
-    a.table = plan->d_t4;
-    a.mel_lo2 = plan->d_lo2;
-    a.n_clips = n_clips;
-    a.clip_stride = clip_stride;
-    a.n_frames = n_frames;
-    a.hop = plan->hop;
-    a.log_floor = plan->log_floor;
-    a.out_scale = 10.f / plan->out_div;
-    a.out_add = plan->out_add;
-    const int64_t blocks = std::min<int64_t>(groups4, persistent_blocks(W == 8 ? 2 : kBlocksPerCU4, stream));
-    const dim3 grid(static_cast<unsigned>(blocks)), block(64 * W);
-    if (W == 8) {
-      if (plan->edge0)
-        hipLaunchKernelGGL((hbk::mel_frames_soa_kernel<true, 8>), grid, block, 0, as_stream(stream), a);
-      else
-        hipLaunchKernelGGL((hbk::mel_frames_soa_kernel<false, 8>), grid, block, 0, as_stream(stream), a);
-    } else {
-      if (plan->edge0)
-        hipLaunchKernelGGL((hbk::mel_frames_soa_kernel<true, 4>), grid, block, 0, as_stream(stream), a);
-      else
-        hipLaunchKernelGGL((hbk::mel_frames_soa_kernel<false, 4>), grid, block, 0, as_stream(stream), a);
+  std::string err;
+  int64_t total = 0;
+  const int rc = mel_call_check(plan->hop, plan->n_fft, pcm, out, n_clips, clip_stride, n_frames, total, err);
+  if (rc != kPlanOk) return plan_error(rc, err);
+  if (total == 0) return HBK_OK;
+  const int route = mel_route(plan->s, plan->s.variant);
+  const MelCall c{plan, pcm, out, n_clips, clip_stride, n_frames, stream,
+                  mel_launch(route, total, persistent_blocks(1, stream))};
+  switch (route) {
+    case 2: {
+      Mel2Args a{};
+      a.window = plan->table<float>(kMelWin);
+      a.tw256 = plan->table<float2>(kMelTw256);
+      a.twsm = plan->table<float2>(kMelTwsm);
+      a.mel_lo2 = plan->table<int>(kMelLo2);
+      a.mel_w2 = plan->table<float>(kMelW2);
+      return mel_run(c, a, kMelV2, "mel_frames_v2_kernel");
     }
-    HBK_LAUNCH_CHECK("mel_frames_soa_kernel");
-    return HBK_OK;
+    case 3: {
+      Mel3Args a{};
+      a.window = plan->table<float>(kMelWin);
+      a.tw256 = plan->table<float2>(kMelTw256);
+      a.twsm = plan->table<float2>(kMelTwsm);
+      a.fbt = plan->table<float>(kMelFbt);
+      return mel_run(c, a, kMelMfma, "mel_frames_mfma_kernel");
+    }
+    case 4:
+    case 8: {
+      Mel4Args a{};
+      a.table = plan->table<float4>(kMelT4);
+      a.mel_lo2 = plan->table<int>(kMelLo2);
+      return mel_run(c, a, route == 8 ? kMelSoa<8> : kMelSoa<4>, "mel_frames_soa_kernel");
+    }
+    default: {
+      MelArgs a{};
+      a.window = plan->table<float>(kMelWin);
+      a.tw256 = plan->table<float2>(kMelTw256);
+      a.tw512 = plan->table<float2>(kMelTw512);
+      a.mel_lo = plan->table<int>(kMelLo);
+      a.mel_w = plan->table<float>(kMelW);
+      a.n_mels = plan->n_mels;
+      a.taps = plan->s.taps;
+      a.nk2 = plan->s.nk2;
+      a.need256 = plan->s.need256;
+      return mel_run(c, a, kMelV1, "mel_frames_kernel");
+    }
   }
-  if (route == 2) {
-    const int64_t groups2 = (total + kFramesPerBlock2 - 1) / kFramesPerBlock2;
-    Mel2Args a;
-    a.pcm = pcm;
-    a.out = out;
-    a.window = plan->d_window;
-    a.tw256 = plan->d_tw256;
-    a.twsm = plan->d_twsm;
-    a.mel_lo2 = plan->d_lo2;
-    a.mel_w2 = plan->d_w2;
-    a.n_clips = n_clips;
-    a.clip_stride = clip_stride;
-    a.n_frames = n_frames;
-    a.hop = plan->hop;
-    a.log_floor = plan->log_floor;
-    a.out_scale = 10.f / plan->out_div;
-    a.out_add = plan->out_add;
-    const int64_t blocks = std::min<int64_t>(groups2, persistent_blocks(kBlocksPerCU2, stream));
-    if (plan->edge0)
-      hipLaunchKernelGGL(HBK_MEL_V2(true), dim3(static_cast<unsigned>(blocks)), dim3(kThreads2), 0,
-                         as_stream(stream), a);
-    else
-      hipLaunchKernelGGL(HBK_MEL_V2(false), dim3(static_cast<unsigned>(blocks)), dim3(kThreads2), 0,
-                         as_stream(stream), a);
-    HBK_LAUNCH_CHECK("mel_frames_v2_kernel");
-    return HBK_OK;
-  }
-  const int64_t groups = (total + kFramesPerBlock - 1) / kFramesPerBlock;
-  MelArgs a;
-  a.pcm = pcm;
-  a.out = out;
-  a.window = plan->d_window;
-  a.tw256 = plan->d_tw256;
-  a.tw512 = plan->d_tw512;
-  a.mel_lo = plan->d_lo;
-  a.mel_w = plan->d_w;
-  a.n_clips = n_clips;
-  a.clip_stride = clip_stride;
-  a.n_frames = n_frames;
-  a.hop = plan->hop;
-  a.n_mels = plan->n_mels;
-  a.taps = plan->taps;
-  a.nk2 = plan->nk2;
-  a.need256 = plan->need256;
-  a.log_floor = plan->log_floor;
-  a.out_div = plan->out_div;
-  a.out_add = plan->out_add;
-  const int64_t blocks = std::min<int64_t>(groups, persistent_blocks(kBlocksPerCU, stream));
-  hipLaunchKernelGGL(mel_frames_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0,
-                     as_stream(stream), a);
-  HBK_LAUNCH_CHECK("mel_frames_kernel");
-  return HBK_OK;
 }
 
 }  // extern "C"
+

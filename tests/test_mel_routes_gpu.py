@@ -177,6 +177,38 @@ def test_nonfinite_sample_under_zero_weight(monkeypatch, masked, route, value):
     assert bad is None, bad
 
 
+def test_two_plans_own_their_tables(monkeypatch, masked):
+    """Each plan holds its tables in one device buffer of its own: two plans alive at once, run
+    interleaved on 3 clips x 23 frames (69 frames: ragged for 16-, 24-, 32- and 64-frame groups), the
+    first switched to the MFMA variant in between and then destroyed; the second one's output does not
+    change by a bit, and every output meets the bound of its case."""
+    n_clips, n_frames, length = 3, 23, 4032
+    first = make_plan(monkeypatch, "v2", "W0", "B0")
+    second = make_plan(monkeypatch, "bank", "W2", "B3")
+    dev1 = torch.tensor(R.clips(R.clips_for("B0"))[:n_clips, :length]).cuda()
+    dev2 = torch.tensor(R.clips(R.clips_for("B3"))[:n_clips, :length]).cuda()
+    sub = (slice(0, n_clips), slice(0, n_frames))
+
+    def check(out, bank_name, window_name):
+        ref, tol, _ = R.case_reference(bank_name, window_name)
+        bad = R.mel_mismatch(out, ref[sub], tol[sub])
+        assert bad is None, bad
+
+    check(run_both(first, dev1, n_frames, masked), "B0", "W0")
+    out2 = run_both(second, dev2, n_frames, masked)
+    check(out2, "B3", "W2")
+    first.set_variant(1)
+    assert first.info()["kernel"] == 3 and second.info()["kernel"] == 1
+    check(run_both(first, dev1, n_frames, masked), "B0", "W0")
+    torch.cuda.synchronize()
+    first.__del__()  # hbk_mel_plan_destroy: the one hipFree of its buffer
+    assert first._handle is None
+    again = run_both(second, dev2, n_frames, masked)
+    check(again, "B3", "W2")
+    assert again.tobytes() == out2.tobytes(), "the second plan's output changed when the first was destroyed"
+    assert np.abs(again[..., R.B3_ZERO_COLUMN] - FLOOR_VALUE).max() <= 1e-6
+
+
 def test_refusals_on_a_plan(monkeypatch):
     from heybuddy import _native
     from heybuddy.kernels import MelPlan
