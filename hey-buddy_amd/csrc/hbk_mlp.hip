@@ -671,6 +671,19 @@ int hbk_mlp_step_variant(const hbk_mlp_plan* p, int64_t batch, void* stream, int
   return HBK_OK;
 }
 
+int hbk_mlp_step_plan_info(const hbk_mlp_plan* p, int64_t batch, void* stream, int32_t* info, int32_t n_info) {
+  using namespace hbk;
+  if (!p || !info) return arg_error("NULL");
+  if (!mlp_fused_supported(*p)) {
+    set_error("hbk: the fused train step covers d_in 1536, layer 96, hidden 64, <= 4 layers");
+    return HBK_ERR_UNSUPPORTED;
+  }
+  if (batch <= 0 || batch > (1 << 22)) return arg_error("batch out of range");
+  if (n_info < kStepPlanInfo) return arg_error("hbk_mlp_step_plan_info: info holds fewer than 19 fields");
+  mlp_fused_step_plan_info(*p, batch, as_stream(stream), info);
+  return HBK_OK;
+}
+
 int hbk_mlp_step_fwd_bwd(const hbk_mlp_plan* p, const float* params, const float* pool32, int64_t n32,
                          const void* pool16, int64_t n16, const int32_t* idx, int64_t idx_step_stride, const float* y, int64_t y_step_stride,
                          int64_t batch, const float* state, int32_t parity, const float* sched, int64_t sched_len,

@@ -2691,6 +2691,18 @@ int mlp_fused_step_variant(int64_t B, hipStream_t s) {
   return step_v2(B, persistent_blocks(1, s), read_step_knobs()) ? 2 : 1;  // (plan_step's variant)
 }
 
+void mlp_fused_step_plan_info(const hbk_mlp_plan& p, int64_t B, hipStream_t s, int32_t info[kStepPlanInfo]) {
+  const int64_t cus = persistent_blocks(1, s);
+  const int NG = static_cast<int>(p.g.size());
+  const StepPlan pl = plan_step(static_cast<int>(B), NG, p.n_params, cus, read_step_knobs());  // (as mlp_fused_run)
+  const bool v2 = pl.variant == 2;
+  const int32_t f[kStepPlanInfo] = {pl.variant, static_cast<int32_t>(pl.Bp), pl.rt, pl.KS, pl.k1_grid, pl.k1c.KC,
+                                    pl.k1c.RT, v2 ? pl.k3s_pair : -1, v2 ? kK3sPairs[pl.k3s_pair][0] : 0,
+                                    v2 ? kK3sPairs[pl.k3s_pair][1] : 0, pl.S0, pl.S1, pl.sparse, pl.slabs,
+                                    pl.pre_tiles, pl.k3_rows, pl.k3_narrow, NG, static_cast<int32_t>(cus)};
+  std::copy(f, f + kStepPlanInfo, info);
+}
+
 WCacheOffsets mlp_wcache_offsets(const hbk_mlp_plan& p) {
   const int NG = static_cast<int>(p.g.size());
   const WSplit wsp = make_wsplit(p);

@@ -74,6 +74,9 @@ int mlp_wcache_fill(const hbk_mlp_plan& p, const float* params, float* cache, hi
 int64_t mlp_fused_ws_floats(const hbk_mlp_plan& p, int64_t B);
 // 1 (k1a / k1b / k3) or 2 (k1s / k1c / k3s): the train step mlp_fused_run takes for B rows on s
 int mlp_fused_step_variant(int64_t B, hipStream_t s);
+// The plan mlp_fused_run takes for B rows on s (hbk_mlp_step_plan_info's fields); launches nothing
+constexpr int kStepPlanInfo = 19;
+void mlp_fused_step_plan_info(const hbk_mlp_plan& p, int64_t B, hipStream_t s, int32_t info[kStepPlanInfo]);
 int mlp_fused_run(const hbk_mlp_plan& p, const float* params, const float* pool32, int64_t n32,
                   const void* pool16, int64_t n16, const int32_t* idx, int64_t idx_stride, int64_t idx_steps,
                   const float* y, int64_t y_stride, int B, const float* state, int parity, const float* sched,

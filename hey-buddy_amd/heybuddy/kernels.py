@@ -482,6 +482,18 @@ class MlpPlan:
                                          ctypes.byref(v)), "hbk_mlp_step_variant")
         return v.value
 
+    STEP_PLAN_FIELDS = ("variant", "Bp", "rt", "KS", "k1_grid", "KC", "RT", "k3s_pair", "NST0", "NST1", "S0", "S1",
+                        "sparse", "slabs", "pre_tiles", "k3_rows", "k3_narrow", "NG", "cus")
+
+    def step_plan_info(self, batch: int, device) -> dict:
+        """The plan step_fwd_bwd takes for ``batch`` rows on ``device``'s current stream, with
+        the knobs as the environment holds them now (hbk_mlp_step_plan_info; nothing is
+        launched): a dict of STEP_PLAN_FIELDS."""
+        buf = (ctypes.c_int32 * len(self.STEP_PLAN_FIELDS))()
+        check(lib().hbk_mlp_step_plan_info(self._handle, int(batch), stream_ptr(torch.device(device)), buf,
+                                           len(buf)), "hbk_mlp_step_plan_info")
+        return dict(zip(self.STEP_PLAN_FIELDS, (int(v) for v in buf)))
+
     @staticmethod
     def new_state(device, adam_t: float = 0.0, salt: int = 0) -> torch.Tensor:
         """Device step state, both halves [0, 1, adam_t, 0, salt, 0, 0, 0]."""

@@ -339,6 +339,15 @@ int hbk_mlp_fused_supported(const hbk_mlp_plan* plan, int32_t* supported);
 /* 1 = k1a/k1b/k3 (v1), 2 = k1s/k1c/k3s (v2): the variant hbk_mlp_step_fwd_bwd
  * takes for `batch` rows on `stream`. Fused plans only. */
 int hbk_mlp_step_variant(const hbk_mlp_plan* plan, int64_t batch, void* stream, int32_t* variant);
+/* The plan hbk_mlp_step_fwd_bwd takes for `batch` rows on `stream`, from the same
+ * planner call (batch, depth, the stream's CUs, the HBK_* knobs as read now); it
+ * launches nothing. info[0..18] (n_info >= 19): variant, Bp (rows padded to the
+ * 16-row tile), rt (row tiles), KS (input-GEMM partial slabs), k1_grid, k1c's KC
+ * and RT (0 in v1), k3s_pair (-1 in v1) with its NST0 and NST1 steps per split,
+ * S0, S1 (the input layer's / generic jobs' splits), sparse, slabs, pre_tiles,
+ * k3_rows and k3_narrow (0 in v2), NG (gated MLPs: layers + 2), the CU count
+ * planned for. Fused plans only. */
+int hbk_mlp_step_plan_info(const hbk_mlp_plan* plan, int64_t batch, void* stream, int32_t* info, int32_t n_info);
 int hbk_mlp_step_fwd_bwd(const hbk_mlp_plan* plan, const float* params, const float* pool32, int64_t n32,
                          const void* pool16, int64_t n16, const int32_t* idx, int64_t idx_step_stride,
                          const float* y, int64_t y_step_stride, int64_t batch, const float* state,

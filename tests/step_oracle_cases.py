@@ -294,8 +294,8 @@ GATED_LR = 2e-4
 GATED_NSEL = (60, 60, 40, 0, 300, 90)
 
 
-def gated_walk(dtype=np.float64, plan=None):
-    """Six steps from Q at B = 800 (200 positives, then 600 negatives) through the oracle
+def gated_walk(dtype=np.float64, plan=None, start=None):
+    """Six steps from ``start`` (default Q) at B = 800 (200 positives, then 600 negatives) through the oracle
     (forward, step_loss_and_dz, backward, Adam and the < 128-sample gate of
     omlp.train_epoch). Before each step the candidates are classified under the float64
     walk's CURRENT parameters and the step's rows composed from U and S, the filtered rows
@@ -303,7 +303,8 @@ def gated_walk(dtype=np.float64, plan=None):
     earlier (float64) walk, replayed in another dtype. Returns a dict: rows [6, 800]
     (candidates), hist [6, 8] (the device history's columns), params, m, fired lrs."""
     w = world()
-    params = OrderedDict((k, np.asarray(v, dtype=dtype)) for k, v in w.Q.items())
+    start = w.Q if start is None else start
+    params = OrderedDict((k, np.asarray(v, dtype=dtype)) for k, v in start.items())
     opt = omlp.Adam(params)
     opt.m = OrderedDict((k, v.astype(dtype)) for k, v in opt.m.items())
     opt.v = OrderedDict((k, v.astype(dtype)) for k, v in opt.v.items())
@@ -353,17 +354,17 @@ def gated_walk(dtype=np.float64, plan=None):
     return {"rows": np.stack(rows_all), "y": y, "hist": hist, "params": params, "m": opt.m, "fired_lr": fired_lr}
 
 
-def gated_figures(params, m, ref) -> dict:
+def gated_figures(params, m, ref, start=None) -> dict:
     """The three multi-step figures of a run against the float64 walk ``ref``: the share of
     parameters differing by > 1e-5, |dP - dP_ref|_2 / |dP_ref|_2 (dP = P_final - P_init)
     and, per tensor, max |m - m_ref| / max |m_ref|; and max |P - P_ref|."""
-    w = world()
-    cat = lambda d: np.concatenate([np.asarray(d[k], np.float64).ravel() for k in w.Q])  # noqa: E731
-    p, pr, p0 = cat(params), cat(ref["params"]), cat(w.Q)
+    start = world().Q if start is None else start  # the walk's initial parameters
+    cat = lambda d: np.concatenate([np.asarray(d[k], np.float64).ravel() for k in start])  # noqa: E731
+    p, pr, p0 = cat(params), cat(ref["params"]), cat(start)
     return {
         "share": float((np.abs(p - pr) > 1e-5).mean()),
         "drift": float(np.linalg.norm((p - p0) - (pr - p0)) / np.linalg.norm(pr - p0)),
         "m": {k: float(np.abs(np.asarray(m[k], np.float64) - ref["m"][k]).max() / np.abs(ref["m"][k]).max())
-              for k in w.Q},
+              for k in start},
         "max": float(np.abs(p - pr).max()),
     }

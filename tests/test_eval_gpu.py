@@ -24,7 +24,7 @@ pytestmark = pytest.mark.gpu
 
 def _model(params):
     from heybuddy.wakeword import WakeWordMLPModel
-    m = WakeWordMLPModel()
+    m = WakeWordMLPModel(num_layers=sum(1 for k in params if k.startswith("layers.") and k.endswith(".0.weight")))
     m.load_state_dict({k: torch.from_numpy(v) for k, v in params.items()}, strict=True)
     return m.cuda()
 
@@ -46,8 +46,10 @@ def _run(plan, flat, pool, rows, label, p=0.0, seed=0, row_offset=0, idx=None):
     return counts.cpu().numpy(), prob.cpu().numpy()
 
 
-def test_eval_probabilities_and_counts_match_oracle():
-    params = omlp.init_params(seed=5)
+@pytest.mark.parametrize("num_layers", [2, 0, 1])
+def test_eval_probabilities_and_counts_match_oracle(num_layers):
+    """At every depth the fused path takes (eval_layout(NG), NG = num_layers + 2)."""
+    params = omlp.init_params(seed=5, num_layers=num_layers)
     p32, p16 = _pools()
     # centre the output bias so that the f16 rows' predictions straddle the threshold
     _, z, _ = omlp.forward(params, p16.astype(np.float32))

@@ -206,13 +206,21 @@ def test_train_indexed_split_with_eval_between_equals_one_call(tmp_path):
         torch.testing.assert_close(s1, s0)
 
 
-@pytest.mark.parametrize("B", [1, 100, 273, 500, 550, 1000, 1100, 2000, 5000])
+@pytest.mark.parametrize("B", [1, 100, 273, 500, 550, 1000, 1100, 2000, 3000, 5000])
 def test_fused_forward_matches_oracle(B):
     """Inference (hbk_mlp_forward: k1a + k1b + k2) against the oracle forward
-    at every K-split of the input GEMM; probabilities within 1e-6."""
+    at every K-split of the input GEMM (k1b_kernel<24 / 16 / 12 / 8 / 6 / 4>: the
+    split of each batch is asserted through hbk_mlp_step_plan_info; the table is
+    step_route_cases.FORWARD_KS, checked against the planner on the CPU by
+    tests/test_step_routes.py); probabilities within 1e-6."""
+    import step_route_cases as rc
     from oracle import mlp as omlp
     params = gc.golden_inputs()[0]
     m = _model(params).eval()
+    info = m.plan.step_plan_info(B, "cuda")
+    print(f"B {B}: plan {info}")
+    assert list(rc.FORWARD_KS) == [1, 100, 273, 500, 550, 1000, 1100, 2000, 3000, 5000]
+    assert (info["variant"], info["KS"]) == (1, rc.FORWARD_KS[B])
     x = (np.random.default_rng(B).standard_normal((B, 16, 96)) * 1.3 + 0.2).astype(np.float32)
     p = m(torch.from_numpy(x).cuda()).cpu().numpy().ravel()
     po, _, _ = omlp.forward(params, x)
