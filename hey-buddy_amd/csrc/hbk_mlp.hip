@@ -14,7 +14,8 @@
 //     b_hg [2H]     (hidden.bias, gate.bias)
 //     W_o  [out, H] (output.weight), b_o [out] (output.bias)
 //   per LN before layers / norm_out: weight, bias [L]
-// The order of blocks follows the forward pass.
+// The order of blocks follows the forward pass. A plan with a half-layer bank
+// (hbk_mlp_plan_create_half) appends the bank after this block: hbk_mlp_half.hip.
 //
 // One train step, without a single host synchronisation:
 //   hbk_mlp_train_fwd_bwd   forward, filter + BCE terms, backward into an
@@ -363,7 +364,7 @@ struct Ws {
   int64_t xn_in, xhat_in, rstd_in;  // [B, D_in] x2, [B]
   std::vector<int64_t> hg, u, s;    // per GMLP: [B,2H], [B,H], [B,out]
   std::vector<int64_t> xn, xhat, rstd;  // per LN (layers + norm_out): [B,L], [B,L], [B]
-  int64_t z, dz, prob, dtmp_a, dtmp_b, dhg, total;
+  int64_t z, dz, prob, dtmp_a, dtmp_b, dhg, half, total;  // half: the bank's own region (half_ws_layout)
 };
 
 Ws ws_layout(const hbk_mlp_plan& p, int64_t B) {
@@ -390,20 +391,21 @@ Ws ws_layout(const hbk_mlp_plan& p, int64_t B) {
   w.dtmp_a = take(B * std::max<int64_t>(wide, p.layer));
   w.dtmp_b = take(B * std::max<int64_t>(wide, p.layer));
   w.dhg = take(B * 2 * p.hid);
+  w.half = take(p.half.n_half > 0 ? half_ws_layout(p.half, B).total : 0);
   w.total = o;
   return w;
 }
 
 template <bool TA, bool TB>
 int gemm(const float* A, const float* B, float* C, const float* bias, int M, int N, int K, int lda,
-         int ldb, int ldc, bool acc, hipStream_t s) {
+         int ldb, int ldc, bool acc, hipStream_t s, bool may_split = true) {
   if (M <= 0 || N <= 0) return HBK_OK;
   dim3 grid((N + GBN - 1) / GBN, (M + GBM - 1) / GBM);
   // Split-K when the output has too few tiles to fill the chip (the weight
   // gradients: K = batch; the input layer: K = 1536), >= 16 K rows per split.
   int splits = 1;
   const int tiles = int(grid.x * grid.y);
-  if (tiles < 256 && K >= 256 && (ldc == N || acc)) splits = std::min(std::max(1, 512 / tiles), K / 16);
+  if (may_split && tiles < 256 && K >= 256 && (ldc == N || acc)) splits = std::min(std::max(1, 512 / tiles), K / 16);
   const int k_split = ((K + splits - 1) / splits + GBK - 1) / GBK * GBK;
   splits = (K + k_split - 1) / k_split;
   if (splits > 1 && !acc) {
@@ -433,6 +435,8 @@ int forward(const hbk_mlp_plan& p, const float* P, const float* x, int B, float*
                      ws + w.xhat_in, ws + w.rstd_in, B, p.d_in, drop_p, seed, step_sc);
   HBK_LAUNCH_CHECK("ln_fwd_kernel");
   const float* in = ws + w.xn_in;
+  // a half plan's forward is bit-reproducible: no split-K (its partial products meet in atomics)
+  const bool split = p.half.n_half == 0;
   for (size_t k = 0; k < p.g.size(); ++k) {
     const Gmlp& gm = p.g[k];
     if (k > 0) {
@@ -445,12 +449,15 @@ int forward(const hbk_mlp_plan& p, const float* P, const float* x, int B, float*
     }
     // HG = in . W_hg^T + b_hg
     HBK_RC((gemm<false, true>(in, P + gm.w_hg, ws + w.hg[k], P + gm.b_hg, B, 2 * gm.hid, gm.in, gm.in, gm.in,
-                              2 * gm.hid, false, s)));
+                              2 * gm.hid, false, s, split)));
     hipLaunchKernelGGL(gate_fwd_kernel, dim3(ew_grid(int64_t(B) * gm.hid)), dim3(256), 0, s, ws + w.hg[k],
                        ws + w.u[k], B, gm.hid);
     HBK_LAUNCH_CHECK("gate_fwd_kernel");
     HBK_RC((gemm<false, true>(ws + w.u[k], P + gm.w_o, ws + w.s[k], P + gm.b_o, B, gm.out, gm.hid, gm.hid,
-                              gm.hid, gm.out, false, s)));
+                              gm.hid, gm.out, false, s, split)));
+    // the half-layer bank adds its branches onto s[0] before the first hidden LayerNorm reads it
+    if (k == 0 && p.half.n_half > 0)
+      HBK_RC(mlp_half_forward(p, P, x, B, ws + w.s[0], ws + w.half, drop_p, seed, step_sc, s));
   }
   return HBK_OK;
 }
@@ -458,7 +465,60 @@ int forward(const hbk_mlp_plan& p, const float* P, const float* x, int B, float*
 }  // namespace
 }  // namespace hbk
 
+namespace hbk {
+namespace {
+// fused-only entry points on a plan they do not cover
+int unsupported(const hbk_mlp_plan& p, const char* what) {
+  if (p.half.n_half > 0)
+    set_error("hbk: %s does not cover half layers (use hbk_mlp_forward / hbk_mlp_train_fwd_bwd)", what);
+  else
+    set_error("hbk: %s covers d_in 1536, layer 96, hidden 64, <= 4 layers", what);
+  return HBK_ERR_UNSUPPORTED;
+}
+}  // namespace
+}  // namespace hbk
+
 extern "C" {
+
+int hbk_mlp_plan_create_half(int32_t d_in, int32_t layer_dim, int32_t hidden, int32_t n_layers, int32_t n_tokens,
+                             int32_t n_half, const int32_t* half_idx, hbk_mlp_plan** plan) {
+  using namespace hbk;
+  if (!plan) return arg_error("plan is NULL");
+  *plan = nullptr;
+  HalfDims d;
+  d.d_in = d_in;
+  d.layer = layer_dim;
+  d.hid = hidden;
+  d.n_tokens = n_tokens;
+  d.n_half = n_half;
+  static const char* const why[] = {"", "bad MLP dims", "n_tokens must be even and in [2, 64]",
+                                    "d_in is not divisible by n_tokens", "half_idx is NULL",
+                                    "half_idx: token index out of range", "half_idx holds more than 256 entries"};
+  const int rule = half_validate(d, half_idx);
+  if (rule) return arg_error(why[rule]);
+  const int rc = hbk_mlp_plan_create(d_in, layer_dim, hidden, n_layers, plan);
+  if (rc) return rc;
+  hbk_mlp_plan* p = *plan;
+  p->half = d;
+  p->half_off = half_offsets(d, p->n_params);
+  p->half_idx.assign(half_idx, half_idx + n_half * d.per());
+  p->n_params += p->half_off.total;
+  return HBK_OK;
+}
+
+int hbk_mlp_half_layout(const hbk_mlp_plan* p, int64_t* offsets, int32_t n_offsets) {
+  using namespace hbk;
+  if (!p || !offsets) return arg_error("NULL");
+  if (p->half.n_half == 0) return arg_error("the plan has no half layers");
+  if (n_offsets < 6 * p->half.n_half) return arg_error("offsets array too small");
+  const HalfOffsets& o = p->half_off;
+  for (int h = 0; h < p->half.n_half; ++h) {
+    const int64_t b = o.base + h * o.stride;
+    const int64_t six[6] = {b + o.g, b + o.b, b + o.w_hg, b + o.b_hg, b + o.w_o, b + o.b_o};
+    for (int i = 0; i < 6; ++i) offsets[6 * h + i] = six[i];
+  }
+  return HBK_OK;
+}
 
 int hbk_mlp_plan_create(int32_t d_in, int32_t layer_dim, int32_t hidden, int32_t n_layers, hbk_mlp_plan** plan) {
   using namespace hbk;
@@ -544,6 +604,7 @@ int hbk_mlp_forward(const hbk_mlp_plan* p, const float* params, const float* x, 
   if (batch < 0 || batch > (1 << 24)) return arg_error("batch out of range");
   if (batch == 0) return HBK_OK;
   if (!params || !x || !prob || !workspace) return arg_error("NULL pointer");
+  if (p->half.n_half > 0 && batch > (1 << 20)) return arg_error("batch out of range (half layers: <= 2^20)");
   const Ws w = ws_layout(*p, batch);
   if (ws_bytes < w.total * int64_t(sizeof(float))) return arg_error("workspace too small");
   hipStream_t s = as_stream(stream);
@@ -574,6 +635,7 @@ int hbk_mlp_train_fwd_bwd(const hbk_mlp_plan* p, const float* params, const floa
   HBK_HIP(hipMemsetAsync(bucket, 0, sizeof(float) * (p->n_params + kStats), s));
   if (batch == 0) return HBK_OK;
   if (!x || !y) return arg_error("NULL x/y");
+  if (p->half.n_half > 0 && batch > (1 << 20)) return arg_error("batch out of range (half layers: <= 2^20)");
   const Ws w = ws_layout(*p, batch);
   if (ws_bytes < w.total * int64_t(sizeof(float))) return arg_error("workspace too small");
   float* ws = static_cast<float*>(workspace);
@@ -596,6 +658,9 @@ int hbk_mlp_train_fwd_bwd(const hbk_mlp_plan* p, const float* params, const floa
   float* bufB = ws + w.dtmp_b;
   for (int k = static_cast<int>(p->g.size()) - 1; k >= 0; --k) {
     const Gmlp& gm = p->g[k];
+    // dS is the gradient at s[0] here: the bank's backward, before this round reuses dS's buffer
+    if (k == 0 && p->half.n_half > 0)
+      HBK_RC(mlp_half_backward(*p, params, x, B, dS, G, ws + w.half, dropout_p, s));
     const float* X = (k == 0) ? ws + w.xn_in : ws + w.xn[k - 1];
     // dW_o [out, H] = dS^T U ; db_o = colsum dS
     // (weight gradients accumulate into the bucket zeroed above: acc = true spares
@@ -663,8 +728,7 @@ int hbk_mlp_step_variant(const hbk_mlp_plan* p, int64_t batch, void* stream, int
   using namespace hbk;
   if (!p || !variant) return arg_error("NULL");
   if (!mlp_fused_supported(*p)) {
-    set_error("hbk: the fused train step covers d_in 1536, layer 96, hidden 64, <= 4 layers");
-    return HBK_ERR_UNSUPPORTED;
+    return unsupported(*p, "the fused train step");
   }
   if (batch <= 0 || batch > (1 << 22)) return arg_error("batch out of range");
   *variant = mlp_fused_step_variant(batch, as_stream(stream));
@@ -675,8 +739,7 @@ int hbk_mlp_step_plan_info(const hbk_mlp_plan* p, int64_t batch, void* stream, i
   using namespace hbk;
   if (!p || !info) return arg_error("NULL");
   if (!mlp_fused_supported(*p)) {
-    set_error("hbk: the fused train step covers d_in 1536, layer 96, hidden 64, <= 4 layers");
-    return HBK_ERR_UNSUPPORTED;
+    return unsupported(*p, "the fused train step");
   }
   if (batch <= 0 || batch > (1 << 22)) return arg_error("batch out of range");
   if (n_info < kStepPlanInfo) return arg_error("hbk_mlp_step_plan_info: info holds fewer than 19 fields");
@@ -693,8 +756,7 @@ int hbk_mlp_step_fwd_bwd(const hbk_mlp_plan* p, const float* params, const float
   using namespace hbk;
   if (!p) return arg_error("plan is NULL");
   if (!mlp_fused_supported(*p)) {
-    set_error("hbk: the fused train step covers d_in 1536, layer 96, hidden 64, <= 4 layers");
-    return HBK_ERR_UNSUPPORTED;
+    return unsupported(*p, "the fused train step");
   }
   if (batch <= 0 || batch > (1 << 22)) return arg_error("batch out of range");
   if (!params || !y || !bucket || !workspace || !state) return arg_error("NULL pointer");
@@ -738,8 +800,7 @@ int hbk_mlp_eval_workspace_size(const hbk_mlp_plan* p, int64_t rows, int64_t* by
   using namespace hbk;
   if (!p || !bytes) return arg_error("NULL");
   if (!mlp_fused_supported(*p)) {
-    set_error("hbk: the evaluation pass covers the fused plans (d_in 1536, layer 96, hidden 64, <= 4 layers)");
-    return HBK_ERR_UNSUPPORTED;
+    return unsupported(*p, "the evaluation pass");
   }
   *bytes = mlp_eval_ws_floats(*p, std::max<int64_t>(rows, 1)) * int64_t(sizeof(float));
   return HBK_OK;
@@ -750,8 +811,7 @@ int hbk_mlp_eval_prepare(const hbk_mlp_plan* p, const float* params, void* works
   using namespace hbk;
   if (!p || !params || !workspace) return arg_error("NULL pointer");
   if (!mlp_fused_supported(*p)) {
-    set_error("hbk: the evaluation pass covers the fused plans");
-    return HBK_ERR_UNSUPPORTED;
+    return unsupported(*p, "the evaluation pass");
   }
   if (ws_bytes < mlp_eval_ws_floats(*p, 1) * int64_t(sizeof(float))) return arg_error("workspace too small");
   return mlp_eval_prepare(*p, params, static_cast<float*>(workspace), as_stream(stream));
@@ -764,8 +824,7 @@ int hbk_mlp_eval_count(const hbk_mlp_plan* p, const float* params, const void* p
   using namespace hbk;
   if (!p || !params || !workspace || !counts) return arg_error("NULL pointer");
   if (!mlp_fused_supported(*p)) {
-    set_error("hbk: the evaluation pass covers the fused plans");
-    return HBK_ERR_UNSUPPORTED;
+    return unsupported(*p, "the evaluation pass");
   }
   if (rows < 0 || row_offset < 0 || rows + row_offset > (int64_t(1) << 31) / 768) return arg_error("rows out of range");
   if (rows == 0) return HBK_OK;
@@ -794,8 +853,7 @@ int hbk_mlp_eval_count_multi(const hbk_mlp_plan* p, const float* params, int32_t
   using namespace hbk;
   if (!p || !params || !workspace) return arg_error("NULL pointer");
   if (!mlp_fused_supported(*p)) {
-    set_error("hbk: the evaluation pass covers the fused plans");
-    return HBK_ERR_UNSUPPORTED;
+    return unsupported(*p, "the evaluation pass");
   }
   if (n_pools < 0 || n_pools > kEvalMaxSeg) return arg_error("n_pools must be in [0, 4]");
   if (n_pools == 0) return HBK_OK;

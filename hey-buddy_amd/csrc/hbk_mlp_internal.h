@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "hbk_mlp_dims.h"
+#include "hbk_mlp_half_plan.h"
 
 namespace hbk {
 
@@ -29,6 +30,11 @@ struct hbk_mlp_plan {
   std::vector<hbk::Gmlp> g;  // mlp_in, layers..., mlp_out
   std::vector<hbk::Ln> ln;   // layers' LNs..., norm_out
   int64_t n_params = 0;
+  // the half-layer bank (hbk_mlp_plan_create_half; half.n_half = 0: none), its parameters after
+  // the block above, and each branch's token indices [n_half][n_tokens / 2]
+  hbk::HalfDims half;
+  hbk::HalfOffsets half_off{};
+  std::vector<int32_t> half_idx;
   // hbk_mlp_set_step_scalars: device [lr, neg_weight, seed] read by the train
   // kernels in place of their by-value arguments (graph-captured steps)
   const double* step_scalars = nullptr;
@@ -85,6 +91,14 @@ int mlp_fused_run(const hbk_mlp_plan& p, const float* params, const float* pool3
 int mlp_fused_update(const hbk_mlp_plan& p, float* params, float* bucket, float* m, float* v, float* state,
                      int parity, const float* sched, int sched_len, float lr, float b1, float b2, float eps,
                      float* hist, int hist_cap, float* ws, hipStream_t s);
+// Half-layer bank (hbk_mlp_half.hip), called from the generic forward / backward of hbk_mlp.hip.
+// ws: the bank's workspace (half_ws_layout). Forward: s0 [B, layer] += sum_h branch_h(x) and keeps
+// statistics, HG, U and (drop_p > 0) the dropped-out input; backward, after that forward on the same ws
+// with the same drop_p: the bank's gradients from ds0 [B, layer] into bucket G (zeroed).
+int mlp_half_forward(const hbk_mlp_plan& p, const float* params, const float* x, int B, float* s0, float* ws,
+                     float drop_p, uint64_t seed, const double* step_sc, hipStream_t s);
+int mlp_half_backward(const hbk_mlp_plan& p, const float* params, const float* x, int B, const float* ds0,
+                      float* G, float* ws, float drop_p, hipStream_t s);
 // Evaluation passes (validation / testing forwards reduced to prediction counts)
 int64_t mlp_eval_ws_floats(const hbk_mlp_plan& p, int64_t rows);
 int mlp_eval_prepare(const hbk_mlp_plan& p, const float* params, float* ws, hipStream_t s);

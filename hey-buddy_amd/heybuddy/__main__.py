@@ -53,7 +53,7 @@ def main() -> None:
 @click.option("--wandb-entity", type=str, default=None, help="W&B entity to use for logging (outside the hot path: ignored).", show_default=True)
 @click.option("--perceptron", "architecture", flag_value="perceptron", default=DEFAULT_ARCHITECTURE == "perceptron", help="Use a perceptron architecture.", show_default=True)
 @click.option("--transformer", "architecture", flag_value="transformer", default=DEFAULT_ARCHITECTURE == "transformer", help="Use a transformer architecture (not implemented on the MI355X path).", show_default=True)
-@click.option("--use-half-layers/--no-use-half-layers", default=DEFAULT_USE_HALF_LAYERS, is_flag=True, help="Use enumerated striped-attention layers for the perceptron model.", show_default=True)
+@click.option("--use-half-layers/--no-use-half-layers", default=DEFAULT_USE_HALF_LAYERS, is_flag=True, help="Use enumerated striped-attention layers for the perceptron model (16 half-connected branches; trains through the generic HIP step, not the fused one).", show_default=True)
 @click.option("--use-gating/--no-use-gating", default=DEFAULT_USE_GATING, is_flag=True, help="Use gated MLP layers for the perceptron model.", show_default=True)
 @click.option("--layer-dim", type=int, default=DEFAULT_LAYER_DIM, help="Dimension of the linear layers to use for the model.", show_default=True)
 @click.option("--num-layers", type=int, default=DEFAULT_LAYERS, help="The number of perceptron blocks.", show_default=True)

@@ -107,6 +107,8 @@ _PROTOS = {
     "hbk_reverb_plan_set_source": (_c_int, [_vp, _vp, _c_int64, _vp, _vp]),
     "hbk_mlp_set_step_scalars": (_c_int, [_vp, _vp]),
     "hbk_mlp_plan_create": (_c_int, [ctypes.c_int32] * 4 + [ctypes.POINTER(_vp)]),
+    "hbk_mlp_plan_create_half": (_c_int, [ctypes.c_int32] * 6 + [_vp, ctypes.POINTER(_vp)]),
+    "hbk_mlp_half_layout": (_c_int, [_vp, _vp, ctypes.c_int32]),
     "hbk_mlp_plan_destroy": (_c_int, [_vp]),
     "hbk_mlp_layout": (_c_int, [_vp, ctypes.POINTER(_c_int64), _vp, ctypes.c_int32]),
     "hbk_mlp_workspace_size": (_c_int, [_vp, _c_int64, ctypes.POINTER(_c_int64)]),

@@ -354,11 +354,33 @@ class MlpPlan:
     layout, forward, and the two halves of a train step."""
 
     N_STATS = 8
+    # WakeWordMLPModel.half_indices (wakeword.py:278-302): the 8 of 16 embedding rows each
+    # half-connected branch reads, in this order (the last two lists are not ascending)
+    HALF_INDICES = ((0, 1, 2, 3, 4, 5, 6, 7), (8, 9, 10, 11, 12, 13, 14, 15), (0, 1, 2, 3, 8, 9, 10, 11),
+                    (4, 5, 6, 7, 12, 13, 14, 15), (4, 5, 6, 7, 8, 9, 10, 11), (0, 1, 2, 3, 12, 13, 14, 15),
+                    (0, 1, 4, 5, 8, 9, 12, 13), (2, 3, 6, 7, 10, 11, 14, 15), (0, 1, 6, 7, 8, 9, 14, 15),
+                    (2, 3, 4, 5, 10, 11, 12, 13), (0, 2, 4, 6, 8, 10, 12, 14), (1, 3, 5, 7, 9, 11, 13, 15),
+                    (0, 3, 4, 7, 8, 11, 12, 15), (1, 2, 5, 6, 9, 10, 13, 14), (0, 5, 2, 7, 8, 13, 10, 15),
+                    (1, 4, 3, 6, 9, 12, 11, 14))
 
-    def __init__(self, d_in: int = 1536, layer_dim: int = 96, hidden: int = 64, n_layers: int = 2) -> None:
+    def __init__(self, d_in: int = 1536, layer_dim: int = 96, hidden: int = 64, n_layers: int = 2,
+                 half_layers: bool = False, n_tokens: int = 16, half_indices=None) -> None:
+        """``half_layers``: with the half-connected bank (hbk_mlp_plan_create_half) over
+        ``n_tokens`` rows of d_in / n_tokens features, branch h reading rows
+        ``half_indices[h]`` (default HALF_INDICES, which needs 16 rows)."""
         handle = ctypes.c_void_p()
-        check(lib().hbk_mlp_plan_create(d_in, layer_dim, hidden, n_layers, ctypes.byref(handle)),
-              "hbk_mlp_plan_create")
+        self.half_indices = []
+        if half_layers:
+            idx = [list(map(int, r)) for r in (self.HALF_INDICES if half_indices is None else half_indices)]
+            if not idx or any(len(r) != n_tokens // 2 for r in idx):
+                raise ValueError(f"half layers take n_tokens / 2 = {n_tokens // 2} rows per branch")
+            flat_idx = (ctypes.c_int32 * (len(idx) * len(idx[0])))(*[t for r in idx for t in r])
+            check(lib().hbk_mlp_plan_create_half(d_in, layer_dim, hidden, n_layers, n_tokens, len(idx), flat_idx,
+                                                 ctypes.byref(handle)), "hbk_mlp_plan_create_half")
+            self.half_indices = idx
+        else:
+            check(lib().hbk_mlp_plan_create(d_in, layer_dim, hidden, n_layers, ctypes.byref(handle)),
+                  "hbk_mlp_plan_create")
         self._handle = handle
         self.d_in, self.layer_dim, self.hidden, self.n_layers = d_in, layer_dim, hidden, n_layers
         n = ctypes.c_int64()
@@ -367,6 +389,11 @@ class MlpPlan:
         check(lib().hbk_mlp_layout(handle, ctypes.byref(n), offs, n_off), "hbk_mlp_layout")
         self.n_params = n.value
         self.offsets = list(offs)
+        self.half_offsets = []  # per branch: LN g, b, W_hg, b_hg, W_o, b_o (hbk_mlp_half_layout)
+        if self.half_indices:
+            hoffs = (ctypes.c_int64 * (6 * len(self.half_indices)))()
+            check(lib().hbk_mlp_half_layout(handle, hoffs, len(hoffs)), "hbk_mlp_half_layout")
+            self.half_offsets = [list(hoffs[6 * h:6 * h + 6]) for h in range(len(self.half_indices))]
         self._ws: Dict[torch.device, torch.Tensor] = {}
         self.id = _register(self)
 
@@ -386,8 +413,8 @@ class MlpPlan:
         gm = o[2:2 + 4 * (self.n_layers + 2)]
         ln = o[2 + 4 * (self.n_layers + 2):]
 
-        def gmlp(prefix, k, din, dout):
-            w_hg, b_hg, w_o, b_o = gm[4 * k:4 * k + 4]
+        def gmlp(prefix, k, din, dout, offs=None):
+            w_hg, b_hg, w_o, b_o = gm[4 * k:4 * k + 4] if offs is None else offs
             out[f"{prefix}.hidden.weight"] = v(w_hg, H, din)
             out[f"{prefix}.hidden.bias"] = v(b_hg, H)
             out[f"{prefix}.output.weight"] = v(w_o, dout, H)
@@ -396,6 +423,10 @@ class MlpPlan:
             out[f"{prefix}.gate.bias"] = v(b_hg + H, H)
 
         gmlp("mlp_in", 0, D, L)
+        for h, ho in enumerate(self.half_offsets):  # the reference registers them after mlp_in
+            out[f"half_layers.{h}.0.weight"] = v(ho[0], D // 2)
+            out[f"half_layers.{h}.0.bias"] = v(ho[1], D // 2)
+            gmlp(f"half_layers.{h}.1", None, D // 2, L, ho[2:])
         for l in range(self.n_layers):
             out[f"layers.{l}.0.weight"] = v(ln[2 * l], L)
             out[f"layers.{l}.0.bias"] = v(ln[2 * l + 1], L)

@@ -415,10 +415,13 @@ def write_model(path: str, nodes: Sequence[Tuple[str, str, Sequence[str], Sequen
 
 def write_wakeword_onnx(path: str, state_dict: Mapping[str, np.ndarray], num_layers: int,
                         input_shape: Tuple[int, int] = (16, 96), opset_version: int = 19,
-                        eps: float = 1e-5) -> None:
+                        eps: float = 1e-5, half_indices: Sequence[Sequence[int]] = ()) -> None:
     """The default head (flatten > LN > gated MLP > [LN > gated MLP] x L > LN >
     gated MLP > sigmoid) in the node / tensor naming of torch.onnx.export of the
-    reference module (wakeword.py:316-332), weights from ``state_dict``."""
+    reference module (wakeword.py:316-332), weights from ``state_dict``.
+    ``half_indices``: the half-connected layers (wakeword.py:341-342), branch h as
+    Gather (axis 1, int64 index initializer) > Flatten > LN > gated MLP > Add into
+    the states after mlp_in."""
     nodes: List[bytes] = []
 
     def ln(src: str, prefix: str, scope: str) -> str:
@@ -448,6 +451,20 @@ def write_wakeword_onnx(path: str, state_dict: Mapping[str, np.ndarray], num_lay
     flat = "/flatten/Flatten_output_0"
     nodes.append(_node("Flatten", "/flatten/Flatten", ["input"], [flat], [_attr_int("axis", 1)]))
     x = gmlp(ln(flat, "norm_in", "/norm_in"), "mlp_in", "/mlp_in")
+    index_inits = b""
+    for h, rows in enumerate(half_indices):
+        sfx = f"_{h}" if h else ""  # the exporter numbers repeated ops: /Gather, /Gather_1, ...
+        idx = f"/Constant{sfx}_output_0"
+        index_inits += _initializer(idx, np.asarray(list(rows), dtype=np.int64))
+        g = f"/Gather{sfx}_output_0"
+        nodes.append(_node("Gather", f"/Gather{sfx}", ["input", idx], [g], [_attr_int("axis", 1)]))
+        f = f"/flatten_{h + 1}/Flatten_output_0"
+        nodes.append(_node("Flatten", f"/flatten_{h + 1}/Flatten", [g], [f], [_attr_int("axis", 1)]))
+        scope = f"/half_layers.{h}/half_layers.{h}"
+        b = gmlp(ln(f, f"half_layers.{h}.0", f"{scope}.0"), f"half_layers.{h}.1", f"{scope}.1")
+        a = f"/Add{sfx}_output_0"
+        nodes.append(_node("Add", f"/Add{sfx}", [x, b], [a]))
+        x = a
     for l in range(num_layers):
         x = ln(x, f"layers.{l}.0", f"/layers.{l}/layers.{l}.0")
         x = gmlp(x, f"layers.{l}.1", f"/layers.{l}/layers.{l}.1")
@@ -455,7 +472,7 @@ def write_wakeword_onnx(path: str, state_dict: Mapping[str, np.ndarray], num_lay
     nodes.append(_node("Sigmoid", "/sigmoid/Sigmoid", [x], ["output"]))
 
     inits = b"".join(_initializer(k, np.asarray(v, dtype=np.float32)) for k, v in state_dict.items())
-    graph = b"".join(nodes) + _f_str(2, "main_graph") + inits
+    graph = b"".join(nodes) + _f_str(2, "main_graph") + inits + index_inits
     graph += _value_info(11, "input", (1, *input_shape)) + _value_info(12, "output", (1, 1))
     model = _f_varint(1, 9) + _f_str(2, "heybuddy-amd") + _f_str(3, "0.1.0") + _f_bytes(7, graph)
     model += _f_bytes(8, _f_varint(2, opset_version))

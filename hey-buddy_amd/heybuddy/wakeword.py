@@ -7,8 +7,10 @@ strict=True, through heybuddy.util.onnx_util), ``from_file``, ``predict``,
 ``predict_timecodes`` and ``save_onnx``, but its parameters are views into
 ONE flat f32 buffer laid out for libhbk.so, and ``forward`` runs the fused HIP
 forward (hbk_mlp_forward). Training goes through the fused HIP train step
-(heybuddy.trainer), not autograd. Only the default architecture is on the MI355X
-path: gated MLP (DEFAULT_USE_GATING), no half layers, SiLU.
+(heybuddy.trainer), not autograd. On the MI355X path: the gated MLP
+(DEFAULT_USE_GATING) with SiLU, with or without the half-connected layers
+(``use_half_layers``, wakeword.py:211-223; those run the generic kernels of
+hbk_mlp.hip / hbk_mlp_half.hip, not the fused step).
 """
 from __future__ import annotations
 
@@ -60,16 +62,19 @@ class WakeWordMLPModel(nn.Module):
                  use_half_layers: bool = DEFAULT_USE_HALF_LAYERS, dropout: float = 0.1,
                  activation: Optional[str] = "silu") -> None:
         super().__init__()
-        if not use_gating or use_half_layers or activation not in ("silu", "swish"):
-            raise NotImplementedError("the MI355X path implements the default architecture: gated MLP, "
-                                      "no half layers, SiLU")
+        if not use_gating or activation not in ("silu", "swish"):
+            raise NotImplementedError("the MI355X path implements the gated MLP with SiLU (with or without "
+                                      "half layers): no use_gating=False, no other activation")
+        if use_half_layers and input_shape[0] != 16:
+            raise ValueError(f"half layers index 16 embedding rows, input_shape has {input_shape[0]}")
         self.input_shape = tuple(input_shape)
         self.input_features = input_shape[0] * input_shape[1]
         self.use_gating = use_gating
         self.use_half_layers = use_half_layers
         self.layer_dim = layer_dim
         self.num_layers = num_layers
-        self.plan = MlpPlan(self.input_features, layer_dim, get_normalized_dim(layer_dim), num_layers)
+        self.plan = MlpPlan(self.input_features, layer_dim, get_normalized_dim(layer_dim), num_layers,
+                            half_layers=use_half_layers, n_tokens=input_shape[0])
         self.dropout = nn.Dropout(dropout)
         flat = torch.zeros(self.plan.n_params, dtype=torch.float32)
         self._bind(flat, build=True)
@@ -81,6 +86,10 @@ class WakeWordMLPModel(nn.Module):
         if build:
             self.norm_in = _Affine(views["norm_in.weight"], views["norm_in.bias"])
             self.mlp_in = _Gmlp(views, "mlp_in")
+            if self.use_half_layers:  # registered here: the reference's state_dict / parameter order
+                self.half_layers = nn.ModuleList(
+                    nn.ModuleList([_Affine(views[f"half_layers.{h}.0.weight"], views[f"half_layers.{h}.0.bias"]),
+                                   _Gmlp(views, f"half_layers.{h}.1")]) for h in range(len(self.half_indices)))
             self.layers = nn.ModuleList(
                 nn.ModuleList([_Affine(views[f"layers.{l}.0.weight"], views[f"layers.{l}.0.bias"]),
                                _Gmlp(views, f"layers.{l}.1")]) for l in range(self.num_layers))
@@ -91,6 +100,11 @@ class WakeWordMLPModel(nn.Module):
             for name, view in views.items():
                 params[name].data = view
         self._flat = flat
+
+    @property
+    def half_indices(self) -> List[List[int]]:
+        """wakeword.py:278-302: the embedding rows of each half-connected layer ([] without them)."""
+        return [list(r) for r in self.plan.half_indices]
 
     @property
     def flat_parameters(self) -> torch.Tensor:
@@ -154,14 +168,17 @@ class WakeWordMLPModel(nn.Module):
         ``save_onnx`` output) load from their initializers."""
         if str(path).lower().endswith(".onnx"):
             from heybuddy.util.onnx_util import read_initializers
-            state_dict = {k: torch.from_numpy(v) for k, v in read_initializers(path).items()}
+            # (other initializers, such as the half layers' Gather indices, are named like nodes)
+            state_dict = {k: torch.from_numpy(v) for k, v in read_initializers(path).items()
+                          if not k.startswith("/")}
         else:
             state_dict = torch.load(path, weights_only=True, map_location="cpu")
         layer_dim = state_dict["norm_out.weight"].shape[0]
         num_layers = 0
         while f"layers.{num_layers}.0.weight" in state_dict:
             num_layers += 1
-        model = cls(layer_dim=layer_dim, num_layers=num_layers)
+        model = cls(layer_dim=layer_dim, num_layers=num_layers,
+                    use_half_layers="half_layers.0.0.weight" in state_dict)
         model.load_state_dict(state_dict)
         if device is not None:
             model.to(device)
@@ -172,7 +189,8 @@ class WakeWordMLPModel(nn.Module):
         graph (input ``input`` [1, 16, 96], output ``output`` [1, 1])."""
         from heybuddy.util.onnx_util import write_wakeword_onnx
         sd = OrderedDict((k, v.detach().float().cpu().numpy()) for k, v in self.state_dict().items())
-        write_wakeword_onnx(path, sd, self.num_layers, self.input_shape, opset_version=opset_version)
+        write_wakeword_onnx(path, sd, self.num_layers, self.input_shape, opset_version=opset_version,
+                            half_indices=self.half_indices)
 
     # -- WakeWordInferenceMixin.predict (wakeword.py:129-169) ---------------
     @property

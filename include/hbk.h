@@ -237,6 +237,23 @@ int hbk_mlp_plan_destroy(hbk_mlp_plan* plan);
 int hbk_mlp_layout(const hbk_mlp_plan* plan, int64_t* n_params, int64_t* offsets, int32_t n_offsets);
 int hbk_mlp_workspace_size(const hbk_mlp_plan* plan, int64_t batch, int64_t* bytes);
 
+/* The same classifier with a half-layer bank (use_half_layers, wakeword.py:211-223, :334-348):
+ * n_half branches LayerNorm(d_in / 2) -> gated MLP(d_in / 2 -> hidden -> layer_dim), added onto
+ * mlp_in's output. A flattened input row is n_tokens chunks of d_in / n_tokens; branch h reads
+ * the n_tokens / 2 chunks half_idx[h * n_tokens / 2 ...] names, in that order, of the same
+ * dropped-out input as norm_in. The first block of the parameter buffer is exactly
+ * hbk_mlp_plan_create's (hbk_mlp_layout reports it, n_params counts the bank too); the bank
+ * follows it. Rejected: d_in not divisible by n_tokens, an odd n_tokens or one above 64, an index
+ * outside [0, n_tokens), more than 256 indices. Such a plan runs hbk_mlp_forward,
+ * hbk_mlp_train_fwd_bwd and hbk_mlp_gate_adam; hbk_mlp_fused_supported answers 0 and the
+ * hbk_mlp_step_* / hbk_mlp_eval_* entry points HBK_ERR_UNSUPPORTED. */
+int hbk_mlp_plan_create_half(int32_t d_in, int32_t layer_dim, int32_t hidden, int32_t n_layers,
+                             int32_t n_tokens, int32_t n_half, const int32_t* half_idx,
+                             hbk_mlp_plan** plan);
+/* Float offsets of the bank, 6 per branch: LayerNorm g, b [d_in / 2]; W_hg [2H, d_in / 2]
+ * (hidden rows then gate rows), b_hg [2H], W_o [layer_dim, H], b_o [layer_dim]. */
+int hbk_mlp_half_layout(const hbk_mlp_plan* plan, int64_t* offsets, int32_t n_offsets);
+
 /* x [batch, d_in] f32 -> prob [batch] (and pre-sigmoid logit [batch] if non-NULL).
  * dropout_p: input dropout (nn.Dropout before the first LayerNorm; the
  * reference keeps it active in training AND validation since .eval() is never
