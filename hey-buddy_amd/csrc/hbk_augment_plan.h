@@ -108,12 +108,19 @@ inline int pitch_geometry(int64_t L, int32_t sample_rate, int32_t num, int32_t d
   a.nw = static_cast<int>(new_sr / g);
   a.width = static_cast<int>(std::ceil(6.0 * a.orig / (std::min(a.orig, a.nw) * 0.99)));
   a.target = static_cast<int>(std::ceil(double(a.nw) * a.l1 / a.orig));
-  // a group of kPvGroup output frames reads at most rate * kPvGroup + 2 new source frames
-  if (a.nw > kPsPhaseMax || 2 * a.width + a.orig > kPsTapMax || a.l1 <= 0 ||
-      a.rate * kPvGroup + 3 > kPvRows) {
+  if (a.nw > kPsPhaseMax || 2 * a.width + a.orig > kPsTapMax || a.l1 <= 0) {
     err = strf("hbk: pitch shift %d/%d resamples %d -> %d (%d taps): the kernel holds <= %d phases of <= %d taps "
                "(torch_pitch_shift's fast shifts at 16 kHz)", num, den, a.orig, a.nw, 2 * a.width + a.orig,
                kPsPhaseMax, kPsTapMax);
+    return kPlanErrUnsupported;
+  }
+  // ps_vocoder_kernel advances the source frame by at most two per output frame (so a group of kPvGroup
+  // output frames reads at most 2 kPvGroup + 2 new source frames); torch_pitch_shift.get_fast_shifts
+  // keeps ratios in [0.5, 2], so the reference never asks for more
+  static_assert(2 * kPvGroup + 3 <= kPvRows, "the d rows of a group at rate 2");
+  if (a.rate > 2.0) {
+    err = strf("hbk: pitch shift %d/%d has rate %g > 2: the vocoder steps at most two source frames per output "
+               "frame (torch_pitch_shift keeps ratios in [0.5, 2])", num, den, a.rate);
     return kPlanErrUnsupported;
   }
   return kPlanOk;

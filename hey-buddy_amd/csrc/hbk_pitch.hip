@@ -759,7 +759,9 @@ ps_vocoder_kernel(PitchArgs a) {
 #endif
       tz = pv_cmul(tz, e7);
     };
-    bool full = t0 + kPvGroup <= a.f_out;
+    // (not the group of frame 0, which has no step: there c = i0(0), not i0(t0 - 1), and at a rate in
+    // [8/7, 9/7), 4/5 and 25/32 of the fast shifts, the seven steps of frames 1 .. 7 total kPvGroup as well)
+    bool full = t0 > 0 && t0 + kPvGroup <= a.f_out;
     if (full) {  // per-frame advances are all >= 1 (rate > 1) or all <= 1 (rate < 1): a total of
       float al;  // kPvGroup means every frame of the group steps exactly once
       full = ps_i0(a, t0 + kPvGroup - 1, al) - c == kPvGroup;

@@ -559,8 +559,13 @@ int hbk_band_stop(const hbk_reverb_plan* plan, const float* x, int64_t x_stride,
  *   Y = phase_vocoder(X, rate = den / num, adv = linspace(0, 7 pi, 126))
  *   out[r] = Resample(16000, 16000 den / num)(istft(Y)), cropped / zero-padded to T
  * Rows not listed are not touched; out may equal x (all reads of x precede
- * the writes). HBK_ERR_UNSUPPORTED for sample_rate != 16000 or a ratio whose
- * resampler needs more than 128 phases or HBK_PITCH_SHIFT_MAX_TAPS taps.
+ * the writes). T in (125, 2^24]; x_stride, out_stride >= T, rows need no
+ * alignment. HBK_ERR_UNSUPPORTED for sample_rate != 16000, a ratio whose
+ * resampler needs more than 128 phases or HBK_PITCH_SHIFT_MAX_TAPS taps, or
+ * a rate den / num > 2 (the vocoder steps at most two source frames per
+ * output frame; torch_pitch_shift draws ratios in [0.5, 2] only: of its 14
+ * fast shifts at 16 kHz all but 125/64, whose resampler needs 149 taps, are
+ * accepted, and so are ratios above 2 such as 5/2).
  * workspace: hbk_pitch_shift_workspace_size bytes (~0.2 MB per entry at
  * T = 23040; 0 for an unsupported geometry). Device pointers. */
 #define HBK_PITCH_SHIFT_MAX_TAPS 144

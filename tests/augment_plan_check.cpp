@@ -3,6 +3,8 @@
 // workspace layout and launch grids, of the band-stop and colored-noise layouts and of the
 // reverb tables, and prints the geometry, layouts and grids as JSON for the comparison with
 // the recorded table. An invariant that fails is reported on stderr and the exit status is 1.
+// With `L sample_rate num den` quadruples as arguments it checks and prints those pitch cases alone
+// (tests/test_pitch_shapes.py).
 #include "hbk_augment_plan.h"
 
 #include <cinttypes>
@@ -174,7 +176,19 @@ static int64_t check_tables() {
   return checked;
 }
 
-int main() {
+int main(int argc, char** argv) {
+  if (argc > 1) {  // L rate num den quadruples: those pitch cases alone (tests/test_pitch_shapes.py)
+    if ((argc - 1) % 4 != 0) {
+      fprintf(stderr, "usage: %s [L sample_rate num den]...\n", argv[0]);
+      return 2;
+    }
+    printf("{\n \"pitch\": [\n");
+    for (int i = 1; i < argc; i += 4)
+      pitch_case(strtoll(argv[i], nullptr, 10), int32_t(strtol(argv[i + 1], nullptr, 10)),
+                 int32_t(strtol(argv[i + 2], nullptr, 10)), int32_t(strtol(argv[i + 3], nullptr, 10)), i + 4 >= argc);
+    printf(" ]\n}\n");
+    return g_failed;
+  }
   printf("{\n \"pitch\": [\n");
   const int64_t kMax = int64_t(1) << 24;
   pitch_case(23040, 16000, 128, 125, false);
