@@ -16,6 +16,10 @@
 //   per LN before layers / norm_out: weight, bias [L]
 // The order of blocks follows the forward pass. A plan with a half-layer bank
 // (hbk_mlp_plan_create_half) appends the bank after this block: hbk_mlp_half.hip.
+// A plain plan (hbk_mlp_plan_create_ex, gated = 0: the reference's MultiLayerPerceptron)
+// keeps the order without the gate rows: W_h [H, in], b_h [H], W_o, b_o per block. It and a
+// plan with another activation than SiLU run the generic path below with the activation
+// kernels of hbk_mlp_act.hip; gated SiLU keeps gate_fwd_kernel / gate_bwd_kernel.
 //
 // One train step, without a single host synchronisation:
 //   hbk_mlp_train_fwd_bwd   forward, filter + BCE terms, backward into an
@@ -375,7 +379,7 @@ Ws ws_layout(const hbk_mlp_plan& p, int64_t B) {
   w.xhat_in = take(B * p.d_in);
   w.rstd_in = take(B);
   for (const auto& gm : p.g) {
-    w.hg.push_back(take(B * 2 * gm.hid));
+    w.hg.push_back(take(B * gm.wid));
     w.u.push_back(take(B * gm.hid));
     w.s.push_back(take(B * gm.out));
   }
@@ -387,10 +391,11 @@ Ws ws_layout(const hbk_mlp_plan& p, int64_t B) {
   w.z = w.s.back();
   w.dz = take(B);
   w.prob = take(B);
-  const int64_t wide = std::max<int64_t>(p.d_in, 2 * p.hid);
+  const int64_t wid = p.gated ? 2 * p.hid : p.hid;  // every block's Gmlp::wid
+  const int64_t wide = std::max<int64_t>(p.d_in, wid);
   w.dtmp_a = take(B * std::max<int64_t>(wide, p.layer));
   w.dtmp_b = take(B * std::max<int64_t>(wide, p.layer));
-  w.dhg = take(B * 2 * p.hid);
+  w.dhg = take(B * wid);
   w.half = take(p.half.n_half > 0 ? half_ws_layout(p.half, B).total : 0);
   w.total = o;
   return w;
@@ -419,7 +424,7 @@ int gemm(const float* A, const float* B, float* C, const float* bias, int M, int
   return HBK_OK;
 }
 
-inline unsigned ew_grid(int64_t n) { return static_cast<unsigned>(std::min<int64_t>((n + 255) / 256, 4096)); }
+inline unsigned ew_grid(int64_t n) { return mlp_ew_grid(n); }  // (shared with hbk_mlp_act.hip)
 
 #define HBK_RC(x)            \
   do {                       \
@@ -447,12 +452,16 @@ int forward(const hbk_mlp_plan& p, const float* P, const float* x, int B, float*
       HBK_LAUNCH_CHECK("ln_fwd_kernel");
       in = ws + w.xn[k - 1];
     }
-    // HG = in . W_hg^T + b_hg
-    HBK_RC((gemm<false, true>(in, P + gm.w_hg, ws + w.hg[k], P + gm.b_hg, B, 2 * gm.hid, gm.in, gm.in, gm.in,
-                              2 * gm.hid, false, s, split)));
-    hipLaunchKernelGGL(gate_fwd_kernel, dim3(ew_grid(int64_t(B) * gm.hid)), dim3(256), 0, s, ws + w.hg[k],
-                       ws + w.u[k], B, gm.hid);
-    HBK_LAUNCH_CHECK("gate_fwd_kernel");
+    // HG = in . W_hg^T + b_hg ([B, 2H]; a plain plan: H = in . W_h^T + b_h, [B, H])
+    HBK_RC((gemm<false, true>(in, P + gm.w_hg, ws + w.hg[k], P + gm.b_hg, B, gm.wid, gm.in, gm.in, gm.in,
+                              gm.wid, false, s, split)));
+    if (p.default_block()) {
+      hipLaunchKernelGGL(gate_fwd_kernel, dim3(ew_grid(int64_t(B) * gm.hid)), dim3(256), 0, s, ws + w.hg[k],
+                         ws + w.u[k], B, gm.hid);
+      HBK_LAUNCH_CHECK("gate_fwd_kernel");
+    } else {
+      HBK_RC(mlp_act_forward(p.act, p.gated, ws + w.hg[k], ws + w.u[k], B, gm.hid, s));
+    }
     HBK_RC((gemm<false, true>(ws + w.u[k], P + gm.w_o, ws + w.s[k], P + gm.b_o, B, gm.out, gm.hid, gm.hid,
                               gm.hid, gm.out, false, s, split)));
     // the half-layer bank adds its branches onto s[0] before the first hidden LayerNorm reads it
@@ -471,6 +480,9 @@ namespace {
 int unsupported(const hbk_mlp_plan& p, const char* what) {
   if (p.half.n_half > 0)
     set_error("hbk: %s does not cover half layers (use hbk_mlp_forward / hbk_mlp_train_fwd_bwd)", what);
+  else if (!p.default_block())
+    set_error("hbk: %s covers the gated SiLU MLP only, not a plain MLP or another activation (use "
+              "hbk_mlp_forward / hbk_mlp_train_fwd_bwd)", what);
   else
     set_error("hbk: %s covers d_in 1536, layer 96, hidden 64, <= 4 layers", what);
   return HBK_ERR_UNSUPPORTED;
@@ -521,22 +533,32 @@ int hbk_mlp_half_layout(const hbk_mlp_plan* p, int64_t* offsets, int32_t n_offse
 }
 
 int hbk_mlp_plan_create(int32_t d_in, int32_t layer_dim, int32_t hidden, int32_t n_layers, hbk_mlp_plan** plan) {
+  return hbk_mlp_plan_create_ex(d_in, layer_dim, hidden, n_layers, 1, HBK_ACT_SILU, plan);
+}
+
+int hbk_mlp_plan_create_ex(int32_t d_in, int32_t layer_dim, int32_t hidden, int32_t n_layers, int32_t gated,
+                           int32_t activation, hbk_mlp_plan** plan) {
   using namespace hbk;
   if (!plan) return arg_error("plan is NULL");
   *plan = nullptr;
   if (d_in <= 0 || layer_dim <= 0 || hidden <= 0 || n_layers < 0) return arg_error("bad MLP dims");
+  if (gated != 0 && gated != 1) return arg_error("gated must be 0 or 1");
+  if (!act_valid(activation)) return arg_error("unknown activation code");
   auto* p = new hbk_mlp_plan();
   p->d_in = d_in;
   p->layer = layer_dim;
   p->hid = hidden;
   p->n_layers = n_layers;
+  p->gated = gated != 0;
+  p->act = activation;
+  const int wid = gated ? 2 * hidden : hidden;
   int64_t o = 0;
   p->ln_in = Ln{d_in, o, o + d_in};
   o += 2 * int64_t(d_in);
   auto add_gmlp = [&](int in, int out) {
-    Gmlp gm{in, hidden, out, 0, 0, 0, 0};
-    gm.w_hg = o; o += int64_t(2) * hidden * in;
-    gm.b_hg = o; o += 2 * hidden;
+    Gmlp gm{in, hidden, out, 0, 0, 0, 0, wid};
+    gm.w_hg = o; o += int64_t(wid) * in;
+    gm.b_hg = o; o += wid;
     gm.w_o = o; o += int64_t(out) * hidden;
     gm.b_o = o; o += out;
     p->g.push_back(gm);
@@ -672,16 +694,20 @@ int hbk_mlp_train_fwd_bwd(const hbk_mlp_plan* p, const float* params, const floa
     // dU [B, H] = dS W_o
     HBK_RC((gemm<false, false>(dS, params + gm.w_o, bufA, nullptr, B, gm.hid, gm.out, gm.out, gm.hid, gm.hid,
                                false, s)));
-    hipLaunchKernelGGL(gate_bwd_kernel, dim3(ew_grid(int64_t(B) * gm.hid)), dim3(256), 0, s, bufA, ws + w.hg[k],
-                       ws + w.dhg, B, gm.hid);
-    HBK_LAUNCH_CHECK("gate_bwd_kernel");
-    // dW_hg [2H, in] = dHG^T X ; db_hg = colsum dHG
-    HBK_RC((gemm<true, false>(ws + w.dhg, X, G + gm.w_hg, nullptr, 2 * gm.hid, gm.in, B, 2 * gm.hid, gm.in,
+    if (p->default_block()) {
+      hipLaunchKernelGGL(gate_bwd_kernel, dim3(ew_grid(int64_t(B) * gm.hid)), dim3(256), 0, s, bufA,
+                         ws + w.hg[k], ws + w.dhg, B, gm.hid);
+      HBK_LAUNCH_CHECK("gate_bwd_kernel");
+    } else {
+      HBK_RC(mlp_act_backward(p->act, p->gated, bufA, ws + w.hg[k], ws + w.dhg, B, gm.hid, s));
+    }
+    // dW_hg [2H, in] = dHG^T X ; db_hg = colsum dHG (a plain plan: dW_h [H, in], db_h from dH)
+    HBK_RC((gemm<true, false>(ws + w.dhg, X, G + gm.w_hg, nullptr, gm.wid, gm.in, B, gm.wid, gm.in,
                               gm.in, true, s)));
-    hipLaunchKernelGGL(colsum_kernel, dim3(cs_grid), dim3(128), 0, s, ws + w.dhg, G + gm.b_hg, B, 2 * gm.hid, rpb);
+    hipLaunchKernelGGL(colsum_kernel, dim3(cs_grid), dim3(128), 0, s, ws + w.dhg, G + gm.b_hg, B, gm.wid, rpb);
     HBK_LAUNCH_CHECK("colsum_kernel");
     // dX [B, in] = dHG W_hg
-    HBK_RC((gemm<false, false>(ws + w.dhg, params + gm.w_hg, bufB, nullptr, B, gm.in, 2 * gm.hid, 2 * gm.hid,
+    HBK_RC((gemm<false, false>(ws + w.dhg, params + gm.w_hg, bufB, nullptr, B, gm.in, gm.wid, gm.wid,
                                gm.in, gm.in, false, s)));
     // LayerNorm in front of this GMLP
     const Ln& l = (k == 0) ? p->ln_in : p->ln[k - 1];
@@ -786,6 +812,7 @@ int hbk_mlp_step_update(const hbk_mlp_plan* p, float* params, float* bucket, flo
                         void* stream) {
   using namespace hbk;
   if (!p) return arg_error("plan is NULL");
+  if (!p->default_block()) return unsupported(*p, "the fused train step");
   if (!params || !bucket || !m || !v || !state) return arg_error("NULL pointer");
   if (parity != 0 && parity != 1) return arg_error("parity must be 0 or 1");
   if (sched && sched_len <= 0) return arg_error("sched_len must be > 0");

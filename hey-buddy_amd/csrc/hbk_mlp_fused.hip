@@ -2680,7 +2680,7 @@ int finish_partials(const StepRun& r) {
 
 bool mlp_fused_supported(const hbk_mlp_plan& p) {
   return p.d_in == kD && p.layer == kL && p.hid == kH && static_cast<int>(p.g.size()) <= kMaxG &&
-         p.g.size() >= 2 && p.half.n_half == 0;
+         p.g.size() >= 2 && p.half.n_half == 0 && p.default_block();
 }
 
 int64_t mlp_fused_ws_floats(const hbk_mlp_plan& p, int64_t B) {

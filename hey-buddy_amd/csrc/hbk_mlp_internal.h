@@ -6,8 +6,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <vector>
 
+#include "hbk_mlp_act.h"
 #include "hbk_mlp_dims.h"
 #include "hbk_mlp_half_plan.h"
 
@@ -16,6 +18,9 @@ namespace hbk {
 struct Gmlp {
   int in, hid, out;
   int64_t w_hg, b_hg, w_o, b_o;  // float offsets into the flat parameter buffer
+  // rows of W_hg = columns of HG: 2 hid (hidden rows then gate rows), or hid in a plain plan
+  // (hbk_mlp_plan_create_ex with gated = 0: W_hg / b_hg are hidden.weight / hidden.bias alone)
+  int wid = 0;
 };
 struct Ln {
   int d;
@@ -30,6 +35,12 @@ struct hbk_mlp_plan {
   std::vector<hbk::Gmlp> g;  // mlp_in, layers..., mlp_out
   std::vector<hbk::Ln> ln;   // layers' LNs..., norm_out
   int64_t n_params = 0;
+  // hbk_mlp_plan_create_ex: MultiLayerPerceptron blocks (no gate) when false; the activation
+  // (HBK_ACT_*). Gated SiLU is the default architecture, the only one the fused kernels, the
+  // evaluation passes and the half-layer bank cover.
+  bool gated = true;
+  int act = HBK_ACT_SILU;
+  bool default_block() const { return gated && act == HBK_ACT_SILU; }
   // the half-layer bank (hbk_mlp_plan_create_half; half.n_half = 0: none), its parameters after
   // the block above, and each branch's token indices [n_half][n_tokens / 2]
   hbk::HalfDims half;
@@ -65,6 +76,16 @@ __device__ __forceinline__ float uniform01(uint64_t seed, uint64_t i) {
 __device__ __forceinline__ float adam_step(float mi, float vi, float step_size, float inv_bc2s, float eps) {
   return step_size * mi * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(vi) * inv_bc2s + eps);
 }
+
+// Grid of an elementwise grid-stride kernel over n elements, 256 threads per block
+inline unsigned mlp_ew_grid(int64_t n) { return static_cast<unsigned>(std::min<int64_t>((n + 255) / 256, 4096)); }
+
+// The activation step of one MLP block for any (HBK_ACT_*, gated) pair (hbk_mlp_act.hip).
+// Forward: u [rows, H] = f(H) (* G) from hg [rows, gated ? 2H : H]; backward: dhg of hg's shape
+// from du [rows, H] and the same hg.
+int mlp_act_forward(int act, bool gated, const float* hg, float* u, int rows, int H, hipStream_t s);
+int mlp_act_backward(int act, bool gated, const float* du, const float* hg, float* dhg, int rows, int H,
+                     hipStream_t s);
 
 // True when the fused kernels (train step: hbk_mlp_fused.hip; evaluation passes:
 // hbk_mlp_eval.hip) cover this plan.

@@ -107,6 +107,10 @@ _PROTOS = {
     "hbk_reverb_plan_set_source": (_c_int, [_vp, _vp, _c_int64, _vp, _vp]),
     "hbk_mlp_set_step_scalars": (_c_int, [_vp, _vp]),
     "hbk_mlp_plan_create": (_c_int, [ctypes.c_int32] * 4 + [ctypes.POINTER(_vp)]),
+    "hbk_mlp_plan_create_ex": (_c_int, [ctypes.c_int32] * 6 + [ctypes.POINTER(_vp)]),
+    "hbk_mlp_act_forward": (_c_int, [_vp, _c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp]),
+    "hbk_mlp_act_backward": (_c_int, [_vp, _vp, _c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp,
+                                      _vp]),
     "hbk_mlp_plan_create_half": (_c_int, [ctypes.c_int32] * 6 + [_vp, ctypes.POINTER(_vp)]),
     "hbk_mlp_half_layout": (_c_int, [_vp, _vp, ctypes.c_int32]),
     "hbk_mlp_plan_destroy": (_c_int, [_vp]),

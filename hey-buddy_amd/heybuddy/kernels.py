@@ -13,7 +13,7 @@ import ctypes
 import os
 import itertools
 import threading
-from typing import Dict
+from typing import Dict, Optional
 
 import numpy as np
 import torch
@@ -349,8 +349,59 @@ def embed_windows(windows: torch.Tensor, plan: EmbedPlan) -> torch.Tensor:
     return torch.ops.hbk.embed_windows(windows.contiguous(), plan.id)
 
 
+# get_activation's names (reference util/modeling_util.py:74-115) -> HBK_ACT_* (include/hbk.h)
+ACTIVATIONS = {"silu": 0, "relu": 1, "gelu": 2, "mish": 3, "tanh": 4, "sigmoid": 5, "identity": 6}
+
+
+def activation_name(activation: Optional[str]) -> str:
+    """The canonical name of one of the reference's activation names ("swish" is silu, None
+    identity); any other raises get_activation's ValueError."""
+    name = {"swish": "silu", None: "identity"}.get(activation, activation)
+    if not isinstance(name, str) or name not in ACTIVATIONS:
+        raise ValueError(f"Activation function '{activation}' not found.")
+    return name
+
+
+def _act_args(hg: torch.Tensor, activation: Optional[str], gated: bool, du: Optional[torch.Tensor] = None):
+    code = ACTIVATIONS[activation_name(activation)]
+    if hg.dim() != 2 or hg.dtype != torch.float32 or hg.device.type != "cuda" or not hg.is_contiguous():
+        raise ValueError("hg must be a contiguous f32 [rows, (2) hidden] device tensor")
+    if gated and hg.shape[1] % 2:
+        raise ValueError("gated: hg holds the columns of H, then those of G")
+    hidden = hg.shape[1] // 2 if gated else hg.shape[1]
+    if hidden == 0:
+        raise ValueError("hidden must be > 0")
+    if du is not None and (tuple(du.shape) != (hg.shape[0], hidden) or du.dtype != torch.float32
+                           or du.device != hg.device or not du.is_contiguous()):
+        raise ValueError(f"du must be a contiguous f32 [{hg.shape[0]}, {hidden}] tensor on {hg.device}")
+    return code, hidden
+
+
+def mlp_activation(hg: torch.Tensor, activation: Optional[str] = "silu", gated: bool = True) -> torch.Tensor:
+    """The activation step of one MLP block (hbk_mlp_act_forward): U [rows, H] = f(H) * G from
+    ``hg`` [rows, 2H] (columns H, then G) when ``gated``, else f(H) from ``hg`` [rows, H]."""
+    code, hidden = _act_args(hg, activation, gated)
+    u = torch.empty((hg.shape[0], hidden), dtype=torch.float32, device=hg.device)
+    with torch.cuda.device(hg.device):
+        check(lib().hbk_mlp_act_forward(ptr(hg), hg.shape[0], hidden, int(bool(gated)), code, ptr(u),
+                                        stream_ptr(hg.device)), "hbk_mlp_act_forward")
+    return u
+
+
+def mlp_activation_backward(du: torch.Tensor, hg: torch.Tensor, activation: Optional[str] = "silu",
+                            gated: bool = True) -> torch.Tensor:
+    """Its backward (hbk_mlp_act_backward): dHG of ``hg``'s shape from dU [rows, H]: dH = dU G f'(H)
+    and dG = dU f(H) when ``gated``, else dH = dU f'(H)."""
+    code, hidden = _act_args(hg, activation, gated, du)
+    dhg = torch.empty_like(hg)
+    with torch.cuda.device(hg.device):
+        check(lib().hbk_mlp_act_backward(ptr(du), ptr(hg), hg.shape[0], hidden, int(bool(gated)), code, ptr(dhg),
+                                         stream_ptr(hg.device)), "hbk_mlp_act_backward")
+    return dhg
+
+
 class MlpPlan:
-    """The gated-MLP classifier on the HIP path (hbk_mlp_*): flat parameter
+    """The MLP classifier on the HIP path (hbk_mlp_*): flat parameter
     layout, forward, and the two halves of a train step."""
 
     N_STATS = 8
@@ -364,12 +415,21 @@ class MlpPlan:
                     (1, 4, 3, 6, 9, 12, 11, 14))
 
     def __init__(self, d_in: int = 1536, layer_dim: int = 96, hidden: int = 64, n_layers: int = 2,
-                 half_layers: bool = False, n_tokens: int = 16, half_indices=None) -> None:
+                 half_layers: bool = False, n_tokens: int = 16, half_indices=None, gated: bool = True,
+                 activation: Optional[str] = "silu") -> None:
         """``half_layers``: with the half-connected bank (hbk_mlp_plan_create_half) over
         ``n_tokens`` rows of d_in / n_tokens features, branch h reading rows
-        ``half_indices[h]`` (default HALF_INDICES, which needs 16 rows)."""
+        ``half_indices[h]`` (default HALF_INDICES, which needs 16 rows).
+        ``gated`` / ``activation`` (hbk_mlp_plan_create_ex): plain MLP blocks without the
+        gate when False; one of ACTIVATIONS. Anything but (True, "silu") runs the generic
+        kernels only (``fused`` is False) and excludes ``half_layers``."""
         handle = ctypes.c_void_p()
         self.half_indices = []
+        self.gated = bool(gated)
+        self.activation = activation_name(activation)
+        default_block = self.gated and self.activation == "silu"
+        if half_layers and not default_block:
+            raise ValueError("half layers exist for the gated SiLU MLP only (hbk_mlp_plan_create_half)")
         if half_layers:
             idx = [list(map(int, r)) for r in (self.HALF_INDICES if half_indices is None else half_indices)]
             if not idx or any(len(r) != n_tokens // 2 for r in idx):
@@ -378,6 +438,10 @@ class MlpPlan:
             check(lib().hbk_mlp_plan_create_half(d_in, layer_dim, hidden, n_layers, n_tokens, len(idx), flat_idx,
                                                  ctypes.byref(handle)), "hbk_mlp_plan_create_half")
             self.half_indices = idx
+        elif not default_block:
+            check(lib().hbk_mlp_plan_create_ex(d_in, layer_dim, hidden, n_layers, int(self.gated),
+                                               ACTIVATIONS[self.activation], ctypes.byref(handle)),
+                  "hbk_mlp_plan_create_ex")
         else:
             check(lib().hbk_mlp_plan_create(d_in, layer_dim, hidden, n_layers, ctypes.byref(handle)),
                   "hbk_mlp_plan_create")
@@ -419,8 +483,9 @@ class MlpPlan:
             out[f"{prefix}.hidden.bias"] = v(b_hg, H)
             out[f"{prefix}.output.weight"] = v(w_o, dout, H)
             out[f"{prefix}.output.bias"] = v(b_o, dout)
-            out[f"{prefix}.gate.weight"] = v(w_hg + H * din, H, din)
-            out[f"{prefix}.gate.bias"] = v(b_hg + H, H)
+            if self.gated:  # (a plain plan's W_hg / b_hg hold the hidden rows alone)
+                out[f"{prefix}.gate.weight"] = v(w_hg + H * din, H, din)
+                out[f"{prefix}.gate.bias"] = v(b_hg + H, H)
 
         gmlp("mlp_in", 0, D, L)
         for h, ho in enumerate(self.half_offsets):  # the reference registers them after mlp_in

@@ -16,7 +16,8 @@ plain protobuf: this module walks the wire format directly.
   (``heybuddy.embedding_graph.from_onnx``, ``heybuddy.spectrogram.mel_params_from_onnx``).
 * ``write_wakeword_onnx``: the graph the exporter emits for the default
   gated-MLP head (Flatten, LayerNormalization, Gemm transB=1, Sigmoid, Mul),
-  so heads trained here can be deployed where the reference's are.
+  so heads trained here can be deployed where the reference's are; the plain
+  MLP and the other activations as standard opset-19 ops (ACTIVATION_OPS).
 * ``write_model``: any graph from (op, name, inputs, outputs, attributes)
   nodes and named initializers (the exporters of the embedding and mel graphs).
 
@@ -32,7 +33,7 @@ from typing import Dict, Iterator, List, Mapping, Sequence, Tuple
 import numpy as np
 
 __all__ = ["read_initializers", "read_nodes", "read_model", "OnnxNode", "OnnxModel", "write_model",
-           "write_wakeword_onnx", "sha256_of"]
+           "write_wakeword_onnx", "wakeword_activation", "ACTIVATION_OPS", "sha256_of"]
 
 # TensorProto.DataType -> numpy dtype (the ones a classifier head can hold)
 _DTYPES = {1: np.float32, 6: np.int32, 7: np.int64, 10: np.float16, 11: np.float64}
@@ -413,16 +414,64 @@ def write_model(path: str, nodes: Sequence[Tuple[str, str, Sequence[str], Sequen
         fp.write(model)
 
 
+# the ops each activation is written as (opset 19), in graph order, under <block>/activation/
+ACTIVATION_OPS = {"relu": ("Relu",), "tanh": ("Tanh",), "sigmoid": ("Sigmoid",), "silu": ("Sigmoid", "Mul"),
+                  "mish": ("Softplus", "Tanh", "Mul"), "gelu": ("Div", "Erf", "Add", "Mul", "Mul"), "identity": ()}
+
+
+def wakeword_activation(path: str) -> str:
+    """The activation of a wake-word head file, from the ops of its first block
+    (nodes named /mlp_in/activation/...): a key of ACTIVATION_OPS."""
+    ops = tuple(n.op for n in read_model(path).nodes if n.name.startswith("/mlp_in/activation/"))
+    for name, want in ACTIVATION_OPS.items():
+        if ops == want:
+            return name
+    raise ValueError(f"{path}: the ops {ops} under /mlp_in/activation/ are no known activation")
+
+
 def write_wakeword_onnx(path: str, state_dict: Mapping[str, np.ndarray], num_layers: int,
                         input_shape: Tuple[int, int] = (16, 96), opset_version: int = 19,
-                        eps: float = 1e-5, half_indices: Sequence[Sequence[int]] = ()) -> None:
+                        eps: float = 1e-5, half_indices: Sequence[Sequence[int]] = (), gated: bool = True,
+                        activation: str = "silu") -> None:
     """The default head (flatten > LN > gated MLP > [LN > gated MLP] x L > LN >
     gated MLP > sigmoid) in the node / tensor naming of torch.onnx.export of the
     reference module (wakeword.py:316-332), weights from ``state_dict``.
     ``half_indices``: the half-connected layers (wakeword.py:341-342), branch h as
     Gather (axis 1, int64 index initializer) > Flatten > LN > gated MLP > Add into
-    the states after mlp_in."""
+    the states after mlp_in.
+    ``gated`` False: a block is hidden/Gemm > activation/* > output/Gemm, without the gate
+    Gemm and the block's Mul. ``activation``: a key of ACTIVATION_OPS, written as those
+    standard ops (gelu in its erf form x / sqrt 2 > Erf > + 1 > x * > * 0.5, mish as
+    x * Tanh(Softplus(x)); their scalar constants are initializers named like the
+    exporter's Constant outputs). Only the default graph (gated, silu) is pinned to the
+    exporter's output: torch.onnx.export needs the onnx / onnxscript packages, which this
+    project does not depend on, so it was not run for the other variants; their node NAMES
+    follow its scheme as far as it is known and are not claimed to be identical to what it
+    would emit."""
+    if activation not in ACTIVATION_OPS:
+        raise ValueError(f"Activation function '{activation}' not found.")
     nodes: List[bytes] = []
+    const_inits = b""
+
+    def act(h: str, scope: str) -> str:
+        nonlocal const_inits
+        n_const = 0
+        for i, op in enumerate(ACTIVATION_OPS[activation]):
+            out = f"{scope}/{op}{'_1' if ACTIVATION_OPS[activation][:i].count(op) else ''}_output_0"
+            prev = h if i == 0 else cur
+            if op in ("Div", "Add") or (op == "Mul" and activation == "gelu" and i == 4):
+                value = {"Div": 2.0 ** 0.5, "Add": 1.0, "Mul": 0.5}[op]
+                c = f"{scope}/Constant{'_' + str(n_const) if n_const else ''}_output_0"
+                n_const += 1
+                const_inits += _initializer(c, np.asarray(value, dtype=np.float32))
+                ins = [prev, c]
+            elif op == "Mul":  # x * (what the ops before made of x)
+                ins = [h, prev]
+            else:
+                ins = [prev]
+            nodes.append(_node(op, out[:-len("_output_0")], ins, [out]))
+            cur = out
+        return cur if ACTIVATION_OPS[activation] else h
 
     def ln(src: str, prefix: str, scope: str) -> str:
         out = f"{scope}/LayerNormalization_output_0"
@@ -438,11 +487,9 @@ def write_wakeword_onnx(path: str, state_dict: Mapping[str, np.ndarray], num_lay
         return out
 
     def gmlp(src: str, prefix: str, scope: str) -> str:
-        h = gemm(src, f"{prefix}.hidden", f"{scope}/hidden")
-        s = f"{scope}/activation/Sigmoid_output_0"
-        nodes.append(_node("Sigmoid", f"{scope}/activation/Sigmoid", [h], [s]))
-        a = f"{scope}/activation/Mul_output_0"
-        nodes.append(_node("Mul", f"{scope}/activation/Mul", [h, s], [a]))
+        a = act(gemm(src, f"{prefix}.hidden", f"{scope}/hidden"), f"{scope}/activation")
+        if not gated:
+            return gemm(a, f"{prefix}.output", f"{scope}/output")
         g = gemm(src, f"{prefix}.gate", f"{scope}/gate")
         m = f"{scope}/Mul_output_0"
         nodes.append(_node("Mul", f"{scope}/Mul", [a, g], [m]))
@@ -472,7 +519,7 @@ def write_wakeword_onnx(path: str, state_dict: Mapping[str, np.ndarray], num_lay
     nodes.append(_node("Sigmoid", "/sigmoid/Sigmoid", [x], ["output"]))
 
     inits = b"".join(_initializer(k, np.asarray(v, dtype=np.float32)) for k, v in state_dict.items())
-    graph = b"".join(nodes) + _f_str(2, "main_graph") + inits + index_inits
+    graph = b"".join(nodes) + _f_str(2, "main_graph") + inits + index_inits + const_inits
     graph += _value_info(11, "input", (1, *input_shape)) + _value_info(12, "output", (1, 1))
     model = _f_varint(1, 9) + _f_str(2, "heybuddy-amd") + _f_str(3, "0.1.0") + _f_bytes(7, graph)
     model += _f_bytes(8, _f_varint(2, opset_version))

@@ -7,10 +7,14 @@ strict=True, through heybuddy.util.onnx_util), ``from_file``, ``predict``,
 ``predict_timecodes`` and ``save_onnx``, but its parameters are views into
 ONE flat f32 buffer laid out for libhbk.so, and ``forward`` runs the fused HIP
 forward (hbk_mlp_forward). Training goes through the fused HIP train step
-(heybuddy.trainer), not autograd. On the MI355X path: the gated MLP
-(DEFAULT_USE_GATING) with SiLU, with or without the half-connected layers
-(``use_half_layers``, wakeword.py:211-223; those run the generic kernels of
-hbk_mlp.hip / hbk_mlp_half.hip, not the fused step).
+(heybuddy.trainer), not autograd. The default, the gated MLP
+(DEFAULT_USE_GATING) with SiLU, trains through the fused step. The generic
+kernels of hbk_mlp.hip run the rest of the constructor's choices: the
+half-connected layers (``use_half_layers``, wakeword.py:211-223;
+hbk_mlp_half.hip), the plain MLP (``use_gating=False``,
+modules/multi_layer_perceptron.py:18-74) and every activation get_activation
+names (util/modeling_util.py:74-115; hbk_mlp_act.hip). Half layers combine with
+neither of the latter two.
 """
 from __future__ import annotations
 
@@ -25,7 +29,7 @@ import torch.nn as nn
 from heybuddy import _native
 from heybuddy.constants import (DEFAULT_LAYER_DIM, DEFAULT_LAYERS, DEFAULT_USE_GATING,
                                 DEFAULT_USE_HALF_LAYERS)
-from heybuddy.kernels import MlpPlan
+from heybuddy.kernels import MlpPlan, activation_name
 
 __all__ = ["WakeWordMLPModel", "get_normalized_dim"]
 
@@ -50,31 +54,35 @@ class _Gmlp(nn.Module):
         super().__init__()
         self.hidden = _Affine(views[f"{prefix}.hidden.weight"], views[f"{prefix}.hidden.bias"])
         self.output = _Affine(views[f"{prefix}.output.weight"], views[f"{prefix}.output.bias"])
-        self.gate = _Affine(views[f"{prefix}.gate.weight"], views[f"{prefix}.gate.bias"])
+        if f"{prefix}.gate.weight" in views:  # (a plain MultiLayerPerceptron has none)
+            self.gate = _Affine(views[f"{prefix}.gate.weight"], views[f"{prefix}.gate.bias"])
 
 
 class WakeWordMLPModel(nn.Module):
-    """input > dropout > flatten > LN > gated MLP > [LN > gated MLP] x L > LN >
-    gated MLP > sigmoid (wakeword.py:334-348). Input [B, 16, 96] -> [B, 1]."""
+    """input > dropout > flatten > LN > MLP > [LN > MLP] x L > LN > MLP > sigmoid
+    (wakeword.py:334-348), MLP being the gated block (``use_gating``, the default) or the
+    plain one, with ``activation``. Input [B, 16, 96] -> [B, 1]."""
 
     def __init__(self, input_shape: Tuple[int, int] = (16, 96), layer_dim: int = DEFAULT_LAYER_DIM,
                  num_layers: int = DEFAULT_LAYERS, use_gating: bool = DEFAULT_USE_GATING,
                  use_half_layers: bool = DEFAULT_USE_HALF_LAYERS, dropout: float = 0.1,
                  activation: Optional[str] = "silu") -> None:
         super().__init__()
-        if not use_gating or activation not in ("silu", "swish"):
-            raise NotImplementedError("the MI355X path implements the gated MLP with SiLU (with or without "
-                                      "half layers): no use_gating=False, no other activation")
+        self.activation = activation_name(activation)  # (get_activation's ValueError for an unknown name)
+        if use_half_layers and (not use_gating or self.activation != "silu"):
+            raise NotImplementedError("the MI355X path implements half layers for the gated MLP with SiLU: "
+                                      "not with use_gating=False, not with another activation")
         if use_half_layers and input_shape[0] != 16:
             raise ValueError(f"half layers index 16 embedding rows, input_shape has {input_shape[0]}")
         self.input_shape = tuple(input_shape)
         self.input_features = input_shape[0] * input_shape[1]
-        self.use_gating = use_gating
+        self.use_gating = bool(use_gating)
         self.use_half_layers = use_half_layers
         self.layer_dim = layer_dim
         self.num_layers = num_layers
         self.plan = MlpPlan(self.input_features, layer_dim, get_normalized_dim(layer_dim), num_layers,
-                            half_layers=use_half_layers, n_tokens=input_shape[0])
+                            half_layers=use_half_layers, n_tokens=input_shape[0], gated=self.use_gating,
+                            activation=self.activation)
         self.dropout = nn.Dropout(dropout)
         flat = torch.zeros(self.plan.n_params, dtype=torch.float32)
         self._bind(flat, build=True)
@@ -162,15 +170,20 @@ class WakeWordMLPModel(nn.Module):
         return z
 
     @classmethod
-    def from_file(cls, path: str, device: Optional[torch.device] = None) -> "WakeWordMLPModel":
-        """wakeword.py:249-276: infer layer_dim / num_layers from the state_dict.
-        ``.onnx`` heads (the reference's shipped src/js/models/*.onnx, or
-        ``save_onnx`` output) load from their initializers."""
+    def from_file(cls, path: str, device: Optional[torch.device] = None,
+                  activation: Optional[str] = "silu") -> "WakeWordMLPModel":
+        """wakeword.py:249-276: infer layer_dim / num_layers from the state_dict, and
+        (beyond the reference, whose from_file builds the default blocks only) the half
+        layers and the plain MLP from the presence of their tensors. ``.onnx`` heads (the
+        reference's shipped src/js/models/*.onnx, or ``save_onnx`` output) load from their
+        initializers, the activation from the ops of the graph's first block; a ``.pt``
+        state dict cannot tell its activation: ``activation`` names it."""
         if str(path).lower().endswith(".onnx"):
-            from heybuddy.util.onnx_util import read_initializers
+            from heybuddy.util.onnx_util import read_initializers, wakeword_activation
             # (other initializers, such as the half layers' Gather indices, are named like nodes)
             state_dict = {k: torch.from_numpy(v) for k, v in read_initializers(path).items()
                           if not k.startswith("/")}
+            activation = wakeword_activation(path)
         else:
             state_dict = torch.load(path, weights_only=True, map_location="cpu")
         layer_dim = state_dict["norm_out.weight"].shape[0]
@@ -178,7 +191,8 @@ class WakeWordMLPModel(nn.Module):
         while f"layers.{num_layers}.0.weight" in state_dict:
             num_layers += 1
         model = cls(layer_dim=layer_dim, num_layers=num_layers,
-                    use_half_layers="half_layers.0.0.weight" in state_dict)
+                    use_half_layers="half_layers.0.0.weight" in state_dict,
+                    use_gating="mlp_in.gate.weight" in state_dict, activation=activation)
         model.load_state_dict(state_dict)
         if device is not None:
             model.to(device)
@@ -186,11 +200,12 @@ class WakeWordMLPModel(nn.Module):
 
     def save_onnx(self, path: str, opset_version: int = 19) -> None:
         """wakeword.py:316-332: the head as an ONNX file with the exporter's
-        graph (input ``input`` [1, 16, 96], output ``output`` [1, 1])."""
+        graph (input ``input`` [1, 16, 96], output ``output`` [1, 1]); a plain MLP and the
+        other activations as write_wakeword_onnx describes."""
         from heybuddy.util.onnx_util import write_wakeword_onnx
         sd = OrderedDict((k, v.detach().float().cpu().numpy()) for k, v in self.state_dict().items())
         write_wakeword_onnx(path, sd, self.num_layers, self.input_shape, opset_version=opset_version,
-                            half_indices=self.half_indices)
+                            half_indices=self.half_indices, gated=self.use_gating, activation=self.activation)
 
     # -- WakeWordInferenceMixin.predict (wakeword.py:129-169) ---------------
     @property

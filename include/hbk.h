@@ -237,6 +237,42 @@ int hbk_mlp_plan_destroy(hbk_mlp_plan* plan);
 int hbk_mlp_layout(const hbk_mlp_plan* plan, int64_t* n_params, int64_t* offsets, int32_t n_offsets);
 int hbk_mlp_workspace_size(const hbk_mlp_plan* plan, int64_t batch, int64_t* bytes);
 
+/* The activation of the MLP blocks (util/modeling_util.py:74-115, get_activation), torch's
+ * semantics: gelu is the exact (erf) form, mish x tanh(softplus(x)); "swish" is SILU, None
+ * IDENTITY. */
+typedef enum {
+  HBK_ACT_SILU = 0,
+  HBK_ACT_RELU = 1,
+  HBK_ACT_GELU = 2,
+  HBK_ACT_MISH = 3,
+  HBK_ACT_TANH = 4,
+  HBK_ACT_SIGMOID = 5,
+  HBK_ACT_IDENTITY = 6
+} hbk_activation;
+
+/* hbk_mlp_plan_create with the block type and the activation chosen: gated = 1 builds
+ * GatedMultiLayerPerceptron blocks W_o (f(W_h x + b_h) * (W_g x + b_g)) + b_o, gated = 0
+ * MultiLayerPerceptron blocks W_o f(W_h x + b_h) + b_o (multi_layer_perceptron.py:18-124);
+ * activation: an HBK_ACT_* code (any other: HBK_ERR_ARG). (1, HBK_ACT_SILU) is
+ * hbk_mlp_plan_create's plan. A plain plan's buffer holds per block W_h [H, in], b_h [H],
+ * W_o [out, H], b_o [out]; hbk_mlp_layout keeps 4 offsets per block, the first two then being
+ * hidden.weight / hidden.bias. Every other plan than (1, HBK_ACT_SILU) runs hbk_mlp_forward,
+ * hbk_mlp_train_fwd_bwd and hbk_mlp_gate_adam; hbk_mlp_fused_supported answers 0 and the
+ * hbk_mlp_step_* / hbk_mlp_eval_* entry points HBK_ERR_UNSUPPORTED. The half-layer bank
+ * (hbk_mlp_plan_create_half) exists for (1, HBK_ACT_SILU) only. */
+int hbk_mlp_plan_create_ex(int32_t d_in, int32_t layer_dim, int32_t hidden, int32_t n_layers,
+                           int32_t gated, int32_t activation, hbk_mlp_plan** plan);
+
+/* The activation step of one block on caller-owned device buffers, for any (activation, gated):
+ * forward u [rows, hidden] = f(H) * G from hg [rows, 2 hidden] (columns H then G), or f(H) from
+ * hg [rows, hidden] when gated = 0; backward dhg (hg's shape) from du [rows, hidden] and the
+ * same hg: dH = du * G * f'(H), dG = du * f(H), or dH = du * f'(H). rows <= 2^24,
+ * hidden <= 2^20. */
+int hbk_mlp_act_forward(const float* hg, int64_t rows, int32_t hidden, int32_t gated,
+                        int32_t activation, float* u, void* stream);
+int hbk_mlp_act_backward(const float* du, const float* hg, int64_t rows, int32_t hidden,
+                         int32_t gated, int32_t activation, float* dhg, void* stream);
+
 /* The same classifier with a half-layer bank (use_half_layers, wakeword.py:211-223, :334-348):
  * n_half branches LayerNorm(d_in / 2) -> gated MLP(d_in / 2 -> hidden -> layer_dim), added onto
  * mlp_in's output. A flattened input row is n_tokens chunks of d_in / n_tokens; branch h reads
