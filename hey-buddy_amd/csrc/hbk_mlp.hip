@@ -1,4 +1,4 @@
-// Wake-word classifier (gated MLP) forward + fused train step for gfx950.
+// Wake-word classifier (gated MLP): the generic forward and train step for gfx950.
 //
 // Replaces WakeWordMLPModel.forward (wakeword.py:334-348) and the optimisation
 // path of WakeWordTrainer.train_epoch (trainer.py:380-494): high-loss filter,
@@ -6,20 +6,18 @@
 // (trainer.py:45). Numerics are f32 throughout (GEMMs on
 // v_mfma_f32_16x16x4f32), so logits match the reference within 1e-4.
 //
-// Parameter layout (one flat f32 buffer; the Python module exposes state_dict
-// views into it):
-//   norm_in.{weight,bias} [D_in] x2
-//   per GMLP g in (mlp_in, layers.l.1 ..., mlp_out):
-//     W_hg [2H, in] (rows 0..H-1 = hidden.weight, H..2H-1 = gate.weight)
-//     b_hg [2H]     (hidden.bias, gate.bias)
-//     W_o  [out, H] (output.weight), b_o [out] (output.bias)
-//   per LN before layers / norm_out: weight, bias [L]
-// The order of blocks follows the forward pass. A plan with a half-layer bank
-// (hbk_mlp_plan_create_half) appends the bank after this block: hbk_mlp_half.hip.
-// A plain plan (hbk_mlp_plan_create_ex, gated = 0: the reference's MultiLayerPerceptron)
-// keeps the order without the gate rows: W_h [H, in], b_h [H], W_o, b_o per block. It and a
-// plan with another activation than SiLU run the generic path below with the activation
-// kernels of hbk_mlp_act.hip; gated SiLU keeps gate_fwd_kernel / gate_bwd_kernel.
+// This file holds the generic path, which serves any dims: its kernels (GEMM, LayerNorm, gate,
+// loss, Adam), forward(), the backward loop, the plan constructors and the entry points that run
+// them. It computes no size and no grid itself: the parameter layout (one flat f32 buffer; the
+// Python module exposes state_dict views into it), the workspace regions and every launch's
+// geometry come from hbk_mlp_layout.h, host-only and checked on the CPU. The entry points of the
+// fused train step and of the evaluation passes live beside their kernels, in hbk_mlp_fused.hip
+// and hbk_mlp_eval.hip; hbk_mlp_forward alone routes a plan they cover to mlp_fused_run.
+// A plan with a half-layer bank (hbk_mlp_plan_create_half) appends the bank after the block
+// of hbk_mlp_layout.h: hbk_mlp_half.hip. A plain plan (hbk_mlp_plan_create_ex, gated = 0: the
+// reference's MultiLayerPerceptron) and a plan with another activation than SiLU run the generic
+// path with the activation kernels of hbk_mlp_act.hip; gated SiLU keeps gate_fwd_kernel /
+// gate_bwd_kernel.
 //
 // One train step, without a single host synchronisation:
 //   hbk_mlp_train_fwd_bwd   forward, filter + BCE terms, backward into an
@@ -44,12 +42,11 @@ namespace {
 typedef float f4 __attribute__((ext_vector_type(4)));
 
 constexpr int kStats = 8;  // bucket tail: see hbk.h
-constexpr float kLnEps = 1e-5f;
 
 // ------------------------------------------------------------- GEMM -------
 // C[M,N] (+)= sum_k A(m,k) B(k,n) (+ bias[n]); A(m,k) = TA ? A[k*lda+m] : A[m*lda+k],
 // B(k,n) = TB ? B[n*ldb+k] : B[k*ldb+n]. Tile 64x64x16, 4 waves as 2x2 of 32x32.
-constexpr int GBM = 64, GBN = 64, GBK = 16;
+constexpr int GBM = kGemmTileM, GBN = kGemmTileN, GBK = kGemmTileK;
 
 template <bool TA, bool TB>
 __global__ void __launch_bounds__(256) gemm_kernel(const float* __restrict__ A, const float* __restrict__ B,
@@ -128,19 +125,10 @@ __global__ void __launch_bounds__(256) gemm_kernel(const float* __restrict__ A, 
 }
 
 // ----------------------------------------------------- row kernels --------
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// Input dropout (nn.Dropout, wakeword.py:197/338: zero with prob p, scale by
-// 1/(1-p)) folded into the first LayerNorm's load.
+// Input dropout (dropout_elem) folded into the first LayerNorm's load.
 __device__ __forceinline__ float dropped(const float* xr, int64_t base, int i, float p, float keep_scale,
                                          uint64_t seed) {
-  const float v = xr[i];
-  if (p <= 0.f) return v;
-  return uniform01(seed, static_cast<uint64_t>(base + i)) < p ? 0.f : v * keep_scale;
+  return dropout_elem(xr[i], seed, static_cast<uint64_t>(base + i), p, keep_scale);
 }
 
 // LayerNorm forward, one wave per row: y = xhat * g + b; keeps xhat, rstd.
@@ -209,8 +197,6 @@ __global__ void __launch_bounds__(256) ln_bwd_kernel(const float* __restrict__ d
     for (int i = lane; i < D; i += 64) dx[static_cast<int64_t>(r) * D + i] = rs * (dyr[i] * g[i] - s1 - xr[i] * s2);
   }
 }
-
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
 // U = silu(H) * G from HG [rows, 2H]
 __global__ void gate_fwd_kernel(const float* __restrict__ hg, float* __restrict__ u, int rows, int H) {
@@ -357,74 +343,20 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
   }
 }
 
-}  // namespace
-}  // namespace hbk
-
-namespace hbk {
-namespace {
-
-// Workspace layout for a batch of B rows (floats).
-struct Ws {
-  int64_t xn_in, xhat_in, rstd_in;  // [B, D_in] x2, [B]
-  std::vector<int64_t> hg, u, s;    // per GMLP: [B,2H], [B,H], [B,out]
-  std::vector<int64_t> xn, xhat, rstd;  // per LN (layers + norm_out): [B,L], [B,L], [B]
-  int64_t z, dz, prob, dtmp_a, dtmp_b, dhg, half, total;  // half: the bank's own region (half_ws_layout)
-};
-
-Ws ws_layout(const hbk_mlp_plan& p, int64_t B) {
-  Ws w;
-  int64_t o = 0;
-  auto take = [&](int64_t n) { const int64_t r = o; o += (n + 63) & ~int64_t(63); return r; };
-  w.xn_in = take(B * p.d_in);
-  w.xhat_in = take(B * p.d_in);
-  w.rstd_in = take(B);
-  for (const auto& gm : p.g) {
-    w.hg.push_back(take(B * gm.wid));
-    w.u.push_back(take(B * gm.hid));
-    w.s.push_back(take(B * gm.out));
-  }
-  for (const auto& l : p.ln) {
-    w.xn.push_back(take(B * l.d));
-    w.xhat.push_back(take(B * l.d));
-    w.rstd.push_back(take(B));
-  }
-  w.z = w.s.back();
-  w.dz = take(B);
-  w.prob = take(B);
-  const int64_t wid = p.gated ? 2 * p.hid : p.hid;  // every block's Gmlp::wid
-  const int64_t wide = std::max<int64_t>(p.d_in, wid);
-  w.dtmp_a = take(B * std::max<int64_t>(wide, p.layer));
-  w.dtmp_b = take(B * std::max<int64_t>(wide, p.layer));
-  w.dhg = take(B * wid);
-  w.half = take(p.half.n_half > 0 ? half_ws_layout(p.half, B).total : 0);
-  w.total = o;
-  return w;
-}
-
 template <bool TA, bool TB>
 int gemm(const float* A, const float* B, float* C, const float* bias, int M, int N, int K, int lda,
          int ldb, int ldc, bool acc, hipStream_t s, bool may_split = true) {
   if (M <= 0 || N <= 0) return HBK_OK;
-  dim3 grid((N + GBN - 1) / GBN, (M + GBM - 1) / GBM);
-  // Split-K when the output has too few tiles to fill the chip (the weight
-  // gradients: K = batch; the input layer: K = 1536), >= 16 K rows per split.
-  int splits = 1;
-  const int tiles = int(grid.x * grid.y);
-  if (may_split && tiles < 256 && K >= 256 && (ldc == N || acc)) splits = std::min(std::max(1, 512 / tiles), K / 16);
-  const int k_split = ((K + splits - 1) / splits + GBK - 1) / GBK * GBK;
-  splits = (K + k_split - 1) / k_split;
-  if (splits > 1 && !acc) {
+  const GemmLaunch g = gemm_launch(M, N, K, ldc == N, acc, may_split);
+  if (g.memset_c) {
     hipError_t e = hipMemsetAsync(C, 0, size_t(M) * N * sizeof(float), s);
     if (e != hipSuccess) return hip_error(e, "hipMemsetAsync (split-K)");
   }
-  grid.z = splits;
-  hipLaunchKernelGGL((gemm_kernel<TA, TB>), grid, dim3(256), 0, s, A, B, C, bias, M, N, K, lda, ldb, ldc,
-                     acc ? 1 : 0, k_split);
+  hipLaunchKernelGGL((gemm_kernel<TA, TB>), dim3(g.grid.x, g.grid.y, g.grid.z), dim3(256), 0, s, A, B, C, bias, M,
+                     N, K, lda, ldb, ldc, acc ? 1 : 0, g.k_split);
   HBK_LAUNCH_CHECK("gemm_kernel");
   return HBK_OK;
 }
-
-inline unsigned ew_grid(int64_t n) { return mlp_ew_grid(n); }  // (shared with hbk_mlp_act.hip)
 
 #define HBK_RC(x)            \
   do {                       \
@@ -435,7 +367,7 @@ inline unsigned ew_grid(int64_t n) { return mlp_ew_grid(n); }  // (shared with h
 // Forward pass; fills the workspace (activations kept for backward).
 int forward(const hbk_mlp_plan& p, const float* P, const float* x, int B, float* ws, const Ws& w,
             float drop_p, uint64_t seed, hipStream_t s, const double* step_sc = nullptr) {
-  const unsigned lnb = (B + 3) / 4;
+  const unsigned lnb = mlp_row_grids(B).ln;
   hipLaunchKernelGGL(ln_fwd_kernel, dim3(lnb), dim3(256), 0, s, x, P + p.ln_in.g, P + p.ln_in.b, ws + w.xn_in,
                      ws + w.xhat_in, ws + w.rstd_in, B, p.d_in, drop_p, seed, step_sc);
   HBK_LAUNCH_CHECK("ln_fwd_kernel");
@@ -456,9 +388,7 @@ int forward(const hbk_mlp_plan& p, const float* P, const float* x, int B, float*
     HBK_RC((gemm<false, true>(in, P + gm.w_hg, ws + w.hg[k], P + gm.b_hg, B, gm.wid, gm.in, gm.in, gm.in,
                               gm.wid, false, s, split)));
     if (p.default_block()) {
-      hipLaunchKernelGGL(gate_fwd_kernel, dim3(ew_grid(int64_t(B) * gm.hid)), dim3(256), 0, s, ws + w.hg[k],
-                         ws + w.u[k], B, gm.hid);
-      HBK_LAUNCH_CHECK("gate_fwd_kernel");
+      HBK_RC(mlp_gate_forward(ws + w.hg[k], ws + w.u[k], B, gm.hid, s));
     } else {
       HBK_RC(mlp_act_forward(p.act, p.gated, ws + w.hg[k], ws + w.u[k], B, gm.hid, s));
     }
@@ -472,22 +402,13 @@ int forward(const hbk_mlp_plan& p, const float* P, const float* x, int B, float*
 }
 
 }  // namespace
-}  // namespace hbk
 
-namespace hbk {
-namespace {
-// fused-only entry points on a plan they do not cover
-int unsupported(const hbk_mlp_plan& p, const char* what) {
-  if (p.half.n_half > 0)
-    set_error("hbk: %s does not cover half layers (use hbk_mlp_forward / hbk_mlp_train_fwd_bwd)", what);
-  else if (!p.default_block())
-    set_error("hbk: %s covers the gated SiLU MLP only, not a plain MLP or another activation (use "
-              "hbk_mlp_forward / hbk_mlp_train_fwd_bwd)", what);
-  else
-    set_error("hbk: %s covers d_in 1536, layer 96, hidden 64, <= 4 layers", what);
-  return HBK_ERR_UNSUPPORTED;
+int mlp_gate_forward(const float* hg, float* u, int rows, int H, hipStream_t s) {
+  hipLaunchKernelGGL(gate_fwd_kernel, dim3(mlp_ew_grid(int64_t(rows) * H)), dim3(256), 0, s, hg, u, rows, H);
+  HBK_LAUNCH_CHECK("gate_fwd_kernel");
+  return HBK_OK;
 }
-}  // namespace
+
 }  // namespace hbk
 
 extern "C" {
@@ -551,30 +472,7 @@ int hbk_mlp_plan_create_ex(int32_t d_in, int32_t layer_dim, int32_t hidden, int3
   p->n_layers = n_layers;
   p->gated = gated != 0;
   p->act = activation;
-  const int wid = gated ? 2 * hidden : hidden;
-  int64_t o = 0;
-  p->ln_in = Ln{d_in, o, o + d_in};
-  o += 2 * int64_t(d_in);
-  auto add_gmlp = [&](int in, int out) {
-    Gmlp gm{in, hidden, out, 0, 0, 0, 0, wid};
-    gm.w_hg = o; o += int64_t(wid) * in;
-    gm.b_hg = o; o += wid;
-    gm.w_o = o; o += int64_t(out) * hidden;
-    gm.b_o = o; o += out;
-    p->g.push_back(gm);
-  };
-  auto add_ln = [&](int d) {
-    p->ln.push_back(Ln{d, o, o + d});
-    o += 2 * int64_t(d);
-  };
-  add_gmlp(d_in, layer_dim);
-  for (int l = 0; l < n_layers; ++l) {
-    add_ln(layer_dim);
-    add_gmlp(layer_dim, layer_dim);
-  }
-  add_ln(layer_dim);
-  add_gmlp(layer_dim, 1);
-  p->n_params = o;
+  static_cast<MlpParams&>(*p) = mlp_param_layout(d_in, layer_dim, hidden, n_layers, p->gated);
   *plan = p;
   return HBK_OK;
 }
@@ -612,7 +510,7 @@ int hbk_mlp_layout(const hbk_mlp_plan* p, int64_t* n_params, int64_t* offsets, i
 
 int hbk_mlp_workspace_size(const hbk_mlp_plan* p, int64_t batch, int64_t* bytes) {
   if (!p || !bytes) return hbk::arg_error("NULL");
-  int64_t floats = hbk::ws_layout(*p, std::max<int64_t>(batch, 1)).total;
+  int64_t floats = hbk::ws_layout(*p, p->half, std::max<int64_t>(batch, 1)).total;
   if (hbk::mlp_fused_supported(*p)) floats = std::max(floats, hbk::mlp_fused_ws_floats(*p, batch));
   *bytes = floats * int64_t(sizeof(float));
   return HBK_OK;
@@ -627,7 +525,7 @@ int hbk_mlp_forward(const hbk_mlp_plan* p, const float* params, const float* x, 
   if (batch == 0) return HBK_OK;
   if (!params || !x || !prob || !workspace) return arg_error("NULL pointer");
   if (p->half.n_half > 0 && batch > (1 << 20)) return arg_error("batch out of range (half layers: <= 2^20)");
-  const Ws w = ws_layout(*p, batch);
+  const Ws w = ws_layout(*p, p->half, batch);
   if (ws_bytes < w.total * int64_t(sizeof(float))) return arg_error("workspace too small");
   hipStream_t s = as_stream(stream);
   float* ws = static_cast<float*>(workspace);
@@ -639,7 +537,7 @@ int hbk_mlp_forward(const hbk_mlp_plan* p, const float* params, const float* x, 
                          0.f, 0.f, dropout_p, seed, nullptr, prob, logit, ws, false, 0, s);
   }
   HBK_RC(forward(*p, params, x, B, ws, w, dropout_p, seed, s));
-  hipLaunchKernelGGL(sigmoid_kernel, dim3(ew_grid(B)), dim3(256), 0, s, ws + w.z, prob, B);
+  hipLaunchKernelGGL(sigmoid_kernel, dim3(mlp_ew_grid(B)), dim3(256), 0, s, ws + w.z, prob, B);
   HBK_LAUNCH_CHECK("sigmoid_kernel");
   if (logit) HBK_HIP(hipMemcpyAsync(logit, ws + w.z, sizeof(float) * B, hipMemcpyDeviceToDevice, s));
   return HBK_OK;
@@ -658,7 +556,7 @@ int hbk_mlp_train_fwd_bwd(const hbk_mlp_plan* p, const float* params, const floa
   if (batch == 0) return HBK_OK;
   if (!x || !y) return arg_error("NULL x/y");
   if (p->half.n_half > 0 && batch > (1 << 20)) return arg_error("batch out of range (half layers: <= 2^20)");
-  const Ws w = ws_layout(*p, batch);
+  const Ws w = ws_layout(*p, p->half, batch);
   if (ws_bytes < w.total * int64_t(sizeof(float))) return arg_error("workspace too small");
   float* ws = static_cast<float*>(workspace);
   const int B = static_cast<int>(batch);
@@ -667,15 +565,14 @@ int hbk_mlp_train_fwd_bwd(const hbk_mlp_plan* p, const float* params, const floa
   float* G = bucket;  // gradients, same layout as params
   float* stats = bucket + p->n_params;
   float* pr = prob ? prob : ws + w.prob;
-  hipLaunchKernelGGL(loss_kernel, dim3(std::min<unsigned>((B + 255) / 256, 64)), dim3(256), 0, s, ws + w.z, y, pr,
-                     ws + w.dz, stats, B, neg_weight, high_loss_threshold, activation_threshold, p->step_scalars);
+  const RowGrids rg = mlp_row_grids(B);
+  hipLaunchKernelGGL(loss_kernel, dim3(rg.loss), dim3(256), 0, s, ws + w.z, y, pr, ws + w.dz, stats, B, neg_weight,
+                     high_loss_threshold, activation_threshold, p->step_scalars);
   HBK_LAUNCH_CHECK("loss_kernel");
   // backward: dS = d(output of GMLP k) [B, out]
   const float* dS = ws + w.dz;  // [B,1] for mlp_out
-  // rows per block of the column reductions (LN dgamma/dbeta, bias grads): ~256
-  // blocks at the stage batch sizes (32 rows gave 35 blocks at B = 1100)
-  const int rpb = std::max(4, (B + 255) / 256);
-  const unsigned cs_grid = (B + rpb - 1) / rpb;
+  const int rpb = rg.rpb;  // rows per block of the column reductions (LN dgamma/dbeta, bias grads)
+  const unsigned cs_grid = rg.cs;
   float* bufA = ws + w.dtmp_a;
   float* bufB = ws + w.dtmp_b;
   for (int k = static_cast<int>(p->g.size()) - 1; k >= 0; --k) {
@@ -695,7 +592,7 @@ int hbk_mlp_train_fwd_bwd(const hbk_mlp_plan* p, const float* params, const floa
     HBK_RC((gemm<false, false>(dS, params + gm.w_o, bufA, nullptr, B, gm.hid, gm.out, gm.out, gm.hid, gm.hid,
                                false, s)));
     if (p->default_block()) {
-      hipLaunchKernelGGL(gate_bwd_kernel, dim3(ew_grid(int64_t(B) * gm.hid)), dim3(256), 0, s, bufA,
+      hipLaunchKernelGGL(gate_bwd_kernel, dim3(mlp_ew_grid(int64_t(B) * gm.hid)), dim3(256), 0, s, bufA,
                          ws + w.hg[k], ws + w.dhg, B, gm.hid);
       HBK_LAUNCH_CHECK("gate_bwd_kernel");
     } else {
@@ -738,178 +635,10 @@ int hbk_mlp_gate_adam(const hbk_mlp_plan* p, float* params, const float* bucket,
   hipLaunchKernelGGL(gate_kernel, dim3(1), dim3(64), 0, s, bucket + p->n_params, state, ctrl, history,
                      history_cap, beta1, beta2);
   HBK_LAUNCH_CHECK("gate_kernel");
-  hipLaunchKernelGGL(adam_kernel, dim3(ew_grid(p->n_params)), dim3(256), 0, s, params, bucket, m, v, ctrl,
+  hipLaunchKernelGGL(adam_kernel, dim3(mlp_ew_grid(p->n_params)), dim3(256), 0, s, params, bucket, m, v, ctrl,
                      p->n_params, lr, beta1, beta2, eps, p->step_scalars);
   HBK_LAUNCH_CHECK("adam_kernel");
   return HBK_OK;
-}
-
-int hbk_mlp_fused_supported(const hbk_mlp_plan* p, int32_t* supported) {
-  if (!p || !supported) return hbk::arg_error("NULL");
-  *supported = hbk::mlp_fused_supported(*p) ? 1 : 0;
-  return HBK_OK;
-}
-
-int hbk_mlp_step_variant(const hbk_mlp_plan* p, int64_t batch, void* stream, int32_t* variant) {
-  using namespace hbk;
-  if (!p || !variant) return arg_error("NULL");
-  if (!mlp_fused_supported(*p)) {
-    return unsupported(*p, "the fused train step");
-  }
-  if (batch <= 0 || batch > (1 << 22)) return arg_error("batch out of range");
-  *variant = mlp_fused_step_variant(batch, as_stream(stream));
-  return HBK_OK;
-}
-
-int hbk_mlp_step_plan_info(const hbk_mlp_plan* p, int64_t batch, void* stream, int32_t* info, int32_t n_info) {
-  using namespace hbk;
-  if (!p || !info) return arg_error("NULL");
-  if (!mlp_fused_supported(*p)) {
-    return unsupported(*p, "the fused train step");
-  }
-  if (batch <= 0 || batch > (1 << 22)) return arg_error("batch out of range");
-  if (n_info < kStepPlanInfo) return arg_error("hbk_mlp_step_plan_info: info holds fewer than 19 fields");
-  mlp_fused_step_plan_info(*p, batch, as_stream(stream), info);
-  return HBK_OK;
-}
-
-int hbk_mlp_step_fwd_bwd(const hbk_mlp_plan* p, const float* params, const float* pool32, int64_t n32,
-                         const void* pool16, int64_t n16, const int32_t* idx, int64_t idx_step_stride, const float* y, int64_t y_step_stride,
-                         int64_t batch, const float* state, int32_t parity, const float* sched, int64_t sched_len,
-                         float neg_weight, float high_loss_threshold, float activation_threshold, float dropout_p,
-                         uint64_t seed, float* bucket, float* prob, int64_t idx_steps, int32_t flags,
-                         void* workspace, int64_t ws_bytes, void* stream) {
-  using namespace hbk;
-  if (!p) return arg_error("plan is NULL");
-  if (!mlp_fused_supported(*p)) {
-    return unsupported(*p, "the fused train step");
-  }
-  if (batch <= 0 || batch > (1 << 22)) return arg_error("batch out of range");
-  if (!params || !y || !bucket || !workspace || !state) return arg_error("NULL pointer");
-  if (!idx && !pool32) return arg_error("no rows: idx and pool32 are NULL");
-  if (parity != 0 && parity != 1) return arg_error("parity must be 0 or 1");
-  if (sched && sched_len <= 0) return arg_error("sched_len must be > 0");
-  if (dropout_p < 0.f || dropout_p >= 1.f) return arg_error("dropout_p must be in [0, 1)");
-  if (ws_bytes < mlp_fused_ws_floats(*p, batch) * int64_t(sizeof(float))) return arg_error("workspace too small");
-  if (n32 < 0 || n16 < 0) return arg_error("negative pool size");
-  if (!idx && n32 < batch) return arg_error("idx NULL: pool32 must hold the batch rows");
-  if (flags & ~(HBK_STEP_XHAT_READY | HBK_STEP_PREFETCH_NEXT | HBK_STEP_WEIGHTS_READY | HBK_STEP_DEFER_PARTIALS |
-                HBK_STEP_GATE_SKIP))
-    return arg_error("unknown flags");
-  if ((flags & HBK_STEP_GATE_SKIP) && !(flags & HBK_STEP_DEFER_PARTIALS))
-    return arg_error("HBK_STEP_GATE_SKIP needs HBK_STEP_DEFER_PARTIALS (the update that follows must own the slabs)");
-  if (!pool32 && !pool16) return arg_error("no embedding pool");
-  return mlp_fused_run(*p, params, pool32, n32, pool16, n16, idx, idx_step_stride, idx_steps, y, y_step_stride,
-                       static_cast<int>(batch), state, parity, sched,
-                       static_cast<int>(std::min<int64_t>(sched_len, 1 << 30)), neg_weight, high_loss_threshold,
-                       activation_threshold, dropout_p, seed, bucket, prob, nullptr, static_cast<float*>(workspace),
-                       true, flags, as_stream(stream));
-}
-
-int hbk_mlp_step_update(const hbk_mlp_plan* p, float* params, float* bucket, float* m, float* v, float* state,
-                        int32_t parity, const float* sched, int64_t sched_len, float lr, float beta1, float beta2,
-                        float eps, float* history, int32_t history_cap, void* workspace, int64_t ws_bytes,
-                        void* stream) {
-  using namespace hbk;
-  if (!p) return arg_error("plan is NULL");
-  if (!p->default_block()) return unsupported(*p, "the fused train step");
-  if (!params || !bucket || !m || !v || !state) return arg_error("NULL pointer");
-  if (parity != 0 && parity != 1) return arg_error("parity must be 0 or 1");
-  if (sched && sched_len <= 0) return arg_error("sched_len must be > 0");
-  if (workspace && (!mlp_fused_supported(*p) || ws_bytes < mlp_fused_ws_floats(*p, 1) * int64_t(sizeof(float))))
-    return arg_error("workspace: fused plans only, and at least the weight cache");
-  return mlp_fused_update(*p, params, bucket, m, v, state, parity, sched,
-                          static_cast<int>(std::min<int64_t>(sched_len, 1 << 30)), lr, beta1, beta2, eps, history,
-                          history ? history_cap : 0, static_cast<float*>(workspace), as_stream(stream));
-}
-
-int hbk_mlp_eval_workspace_size(const hbk_mlp_plan* p, int64_t rows, int64_t* bytes) {
-  using namespace hbk;
-  if (!p || !bytes) return arg_error("NULL");
-  if (!mlp_fused_supported(*p)) {
-    return unsupported(*p, "the evaluation pass");
-  }
-  *bytes = mlp_eval_ws_floats(*p, std::max<int64_t>(rows, 1)) * int64_t(sizeof(float));
-  return HBK_OK;
-}
-
-int hbk_mlp_eval_prepare(const hbk_mlp_plan* p, const float* params, void* workspace, int64_t ws_bytes,
-                         void* stream) {
-  using namespace hbk;
-  if (!p || !params || !workspace) return arg_error("NULL pointer");
-  if (!mlp_fused_supported(*p)) {
-    return unsupported(*p, "the evaluation pass");
-  }
-  if (ws_bytes < mlp_eval_ws_floats(*p, 1) * int64_t(sizeof(float))) return arg_error("workspace too small");
-  return mlp_eval_prepare(*p, params, static_cast<float*>(workspace), as_stream(stream));
-}
-
-int hbk_mlp_eval_count(const hbk_mlp_plan* p, const float* params, const void* pool, int32_t pool_is_f16,
-                       int64_t n_pool, const int32_t* idx, int64_t rows, int64_t row_offset, int32_t label,
-                       float activation_threshold, float dropout_p, uint64_t seed, float* counts, float* prob,
-                       void* workspace, int64_t ws_bytes, void* stream) {
-  using namespace hbk;
-  if (!p || !params || !workspace || !counts) return arg_error("NULL pointer");
-  if (!mlp_fused_supported(*p)) {
-    return unsupported(*p, "the evaluation pass");
-  }
-  if (rows < 0 || row_offset < 0 || rows + row_offset > (int64_t(1) << 31) / 768) return arg_error("rows out of range");
-  if (rows == 0) return HBK_OK;
-  if (!pool || n_pool <= 0) return arg_error("empty pool");
-  if (label != 0 && label != 1) return arg_error("label must be 0 or 1");
-  if (dropout_p < 0.f || dropout_p >= 1.f) return arg_error("dropout_p must be in [0, 1)");
-  if (ws_bytes < mlp_eval_ws_floats(*p, rows) * int64_t(sizeof(float))) return arg_error("workspace too small");
-  return mlp_eval_count(*p, params, pool, pool_is_f16 != 0, n_pool, idx, rows, row_offset, label,
-                        activation_threshold, dropout_p, seed, counts, prob, static_cast<float*>(workspace),
-                        as_stream(stream));
-}
-
-int hbk_mlp_eval_laps(int64_t rows, int64_t n_pool, int32_t pool_is_f16, int32_t has_idx, int64_t* parts) {
-  using namespace hbk;
-  if (!parts) return arg_error("NULL pointer");
-  if (rows < 0 || n_pool <= 0) return arg_error("rows / n_pool out of range");
-  mlp_eval_lap_plan(rows, n_pool, pool_is_f16 != 0, has_idx != 0, parts);
-  return HBK_OK;
-}
-
-int hbk_mlp_eval_count_multi(const hbk_mlp_plan* p, const float* params, int32_t n_pools,
-                             const void* const* pools, int32_t pools_are_f16, const int64_t* n_pool,
-                             const int64_t* rows, const int64_t* row_offsets, const int32_t* labels,
-                             const uint64_t* seeds, float* const* counts, float activation_threshold,
-                             float dropout_p, void* workspace, int64_t ws_bytes, void* stream) {
-  using namespace hbk;
-  if (!p || !params || !workspace) return arg_error("NULL pointer");
-  if (!mlp_fused_supported(*p)) {
-    return unsupported(*p, "the evaluation pass");
-  }
-  if (n_pools < 0 || n_pools > kEvalMaxSeg) return arg_error("n_pools must be in [0, 4]");
-  if (n_pools == 0) return HBK_OK;
-  if (!pools || !n_pool || !rows || !row_offsets || !labels || !seeds || !counts) return arg_error("NULL array");
-  if (dropout_p < 0.f || dropout_p >= 1.f) return arg_error("dropout_p must be in [0, 1)");
-  EvalSeg seg[kEvalMaxSeg];
-  int64_t max_rows = 0;
-  for (int i = 0; i < n_pools; ++i) {
-    if (rows[i] < 0 || row_offsets[i] < 0 || rows[i] + row_offsets[i] > (int64_t(1) << 31) / 768)
-      return arg_error("rows out of range");
-    if (rows[i] > 0 && (!pools[i] || n_pool[i] <= 0)) return arg_error("empty pool");
-    if (labels[i] != 0 && labels[i] != 1) return arg_error("label must be 0 or 1");
-    if (rows[i] > 0 && !counts[i]) return arg_error("counts is NULL");
-    seg[i] = EvalSeg{pools[i], n_pool[i], rows[i], row_offsets[i], seeds[i], counts[i], labels[i]};
-    max_rows = std::max(max_rows, rows[i]);
-  }
-  if (ws_bytes < mlp_eval_ws_floats(*p, max_rows) * int64_t(sizeof(float))) return arg_error("workspace too small");
-  return mlp_eval_count_multi(*p, params, pools_are_f16 != 0, seg, n_pools, activation_threshold, dropout_p,
-                              static_cast<float*>(workspace), as_stream(stream));
-}
-
-int hbk_mlp_eval_finish(const float* counts_val, const float* counts_test, const double* sizes,
-                        float target_false_positives_per_hour, float adjust_ratio, float* sched, int64_t sched_len,
-                        int64_t next_step, float* out, void* stream) {
-  using namespace hbk;
-  if (!sizes) return arg_error("sizes is NULL");
-  if (sched && (sched_len <= 0 || next_step < 0)) return arg_error("schedule range");
-  return mlp_eval_finish(counts_val, counts_test, sizes, target_false_positives_per_hour, adjust_ratio, sched,
-                         sched_len, next_step, out, as_stream(stream));
 }
 
 }  // extern "C"

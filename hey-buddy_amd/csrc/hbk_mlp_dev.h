@@ -19,7 +19,6 @@ namespace {
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-constexpr float kLnEps = 1e-5f;
 
 __device__ __forceinline__ f4 mma(float a, float b, f4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);

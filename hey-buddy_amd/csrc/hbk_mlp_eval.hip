@@ -3,7 +3,9 @@
 // (the input GEMM and the rest of the network per row tile, reduced to prediction
 // counts) and kv_finish (rates and the dynamic negative weight). The weight cache
 // is the train step's (k0_wsplit_kernel in hbk_mlp_fused.hip, reached through
-// mlp_wcache_fill); the shared device helpers are in hbk_mlp_dev.h.
+// mlp_wcache_fill); the shared device helpers are in hbk_mlp_dev.h. The passes'
+// entry points (hbk_mlp_eval_*), argument checks included, are at the end of this
+// file; nothing of it is called from another unit.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -34,7 +36,15 @@ namespace {
 // chunks ahead. The pre-bias HG0 rows go to a slab that k2_rows_kernel
 // <false> (the inference chain, with its counters) reads as its one K-split.
 constexpr int kKvKC = 64, kKvChunks = kD / kKvKC;
-constexpr int kKvMaxSeg = kEvalMaxSeg;
+constexpr int kKvMaxSeg = 4;
+// one pool of an evaluation launch (mlp_eval_count_multi: several pools of one dtype in one launch)
+struct EvalSeg {
+  const void* pool;
+  int64_t n_pool, rows, r0;
+  uint64_t seed;
+  float* counts;
+  int label;
+};
 struct KvArgs {
   const void* pool;      // f32 or f16 rows of 1536
   int64_t n_pool;
@@ -651,8 +661,8 @@ EvalWs eval_layout(int NG) {
   return w;
 }
 
-}  // namespace
-
+// Evaluation passes (validation / testing forwards reduced to prediction counts): the launchers
+// behind the entry points below.
 int64_t mlp_eval_ws_floats(const hbk_mlp_plan& p, int64_t rows) {
   (void)rows;  // the passes need no per-row workspace
   return eval_layout(static_cast<int>(p.g.size())).total;
@@ -669,6 +679,7 @@ int mlp_eval_prepare(const hbk_mlp_plan& p, const float* params, float* ws, hipS
   return HBK_OK;
 }
 
+// The rows mlp_eval_count evaluates in the lap form (two laps of the pool together) and in the plain form.
 // How a single-pool pass of `rows` row evaluations is launched: part[0] rows in the lap form (whole sets
 // of two laps, so no set carries a dead lap), part[1] in the plain form. Laps are for f16 pools read in
 // order that the pass covers at least twice. HBK_EVAL_LAPS=0 (read per call, so one process can compare)
@@ -683,7 +694,7 @@ void mlp_eval_lap_plan(int64_t rows, int64_t n_pool, bool f16, bool has_idx, int
 
 // One kv_gemm_kernel launch over nseg pools of one dtype (nseg = 1: the single-pool fields,
 // which also allow idx / prob; nseg > 1: the segment table, workgroups in pool order).
-static int mlp_eval_launch(const hbk_mlp_plan& p, const float* params, bool f16, const EvalSeg* seg, int nseg,
+int mlp_eval_launch(const hbk_mlp_plan& p, const float* params, bool f16, const EvalSeg* seg, int nseg,
                            const int32_t* idx, float act_thr, float drop_p, float* prob, float* ws, hipStream_t s) {
   const int NG = static_cast<int>(p.g.size());
   const EvalWs w = eval_layout(NG);
@@ -801,4 +812,91 @@ int mlp_eval_finish(const float* cv, const float* ct, const double* sizes, float
   return HBK_OK;
 }
 
+}  // namespace
 }  // namespace hbk
+
+// The passes' entry points: argument checks, then the launchers above.
+extern "C" {
+
+int hbk_mlp_eval_workspace_size(const hbk_mlp_plan* p, int64_t rows, int64_t* bytes) {
+  using namespace hbk;
+  if (!p || !bytes) return arg_error("NULL");
+  if (!mlp_fused_supported(*p)) return mlp_unsupported(*p, "the evaluation pass");
+  *bytes = mlp_eval_ws_floats(*p, std::max<int64_t>(rows, 1)) * int64_t(sizeof(float));
+  return HBK_OK;
+}
+
+int hbk_mlp_eval_prepare(const hbk_mlp_plan* p, const float* params, void* workspace, int64_t ws_bytes,
+                         void* stream) {
+  using namespace hbk;
+  if (!p || !params || !workspace) return arg_error("NULL pointer");
+  if (!mlp_fused_supported(*p)) return mlp_unsupported(*p, "the evaluation pass");
+  if (ws_bytes < mlp_eval_ws_floats(*p, 1) * int64_t(sizeof(float))) return arg_error("workspace too small");
+  return mlp_eval_prepare(*p, params, static_cast<float*>(workspace), as_stream(stream));
+}
+
+int hbk_mlp_eval_count(const hbk_mlp_plan* p, const float* params, const void* pool, int32_t pool_is_f16,
+                       int64_t n_pool, const int32_t* idx, int64_t rows, int64_t row_offset, int32_t label,
+                       float activation_threshold, float dropout_p, uint64_t seed, float* counts, float* prob,
+                       void* workspace, int64_t ws_bytes, void* stream) {
+  using namespace hbk;
+  if (!p || !params || !workspace || !counts) return arg_error("NULL pointer");
+  if (!mlp_fused_supported(*p)) return mlp_unsupported(*p, "the evaluation pass");
+  if (rows < 0 || row_offset < 0 || rows + row_offset > (int64_t(1) << 31) / 768) return arg_error("rows out of range");
+  if (rows == 0) return HBK_OK;
+  if (!pool || n_pool <= 0) return arg_error("empty pool");
+  if (label != 0 && label != 1) return arg_error("label must be 0 or 1");
+  if (dropout_p < 0.f || dropout_p >= 1.f) return arg_error("dropout_p must be in [0, 1)");
+  if (ws_bytes < mlp_eval_ws_floats(*p, rows) * int64_t(sizeof(float))) return arg_error("workspace too small");
+  return mlp_eval_count(*p, params, pool, pool_is_f16 != 0, n_pool, idx, rows, row_offset, label,
+                        activation_threshold, dropout_p, seed, counts, prob, static_cast<float*>(workspace),
+                        as_stream(stream));
+}
+
+int hbk_mlp_eval_laps(int64_t rows, int64_t n_pool, int32_t pool_is_f16, int32_t has_idx, int64_t* parts) {
+  using namespace hbk;
+  if (!parts) return arg_error("NULL pointer");
+  if (rows < 0 || n_pool <= 0) return arg_error("rows / n_pool out of range");
+  mlp_eval_lap_plan(rows, n_pool, pool_is_f16 != 0, has_idx != 0, parts);
+  return HBK_OK;
+}
+
+int hbk_mlp_eval_count_multi(const hbk_mlp_plan* p, const float* params, int32_t n_pools,
+                             const void* const* pools, int32_t pools_are_f16, const int64_t* n_pool,
+                             const int64_t* rows, const int64_t* row_offsets, const int32_t* labels,
+                             const uint64_t* seeds, float* const* counts, float activation_threshold,
+                             float dropout_p, void* workspace, int64_t ws_bytes, void* stream) {
+  using namespace hbk;
+  if (!p || !params || !workspace) return arg_error("NULL pointer");
+  if (!mlp_fused_supported(*p)) return mlp_unsupported(*p, "the evaluation pass");
+  if (n_pools < 0 || n_pools > kKvMaxSeg) return arg_error("n_pools must be in [0, 4]");
+  if (n_pools == 0) return HBK_OK;
+  if (!pools || !n_pool || !rows || !row_offsets || !labels || !seeds || !counts) return arg_error("NULL array");
+  if (dropout_p < 0.f || dropout_p >= 1.f) return arg_error("dropout_p must be in [0, 1)");
+  EvalSeg seg[kKvMaxSeg];
+  int64_t max_rows = 0;
+  for (int i = 0; i < n_pools; ++i) {
+    if (rows[i] < 0 || row_offsets[i] < 0 || rows[i] + row_offsets[i] > (int64_t(1) << 31) / 768)
+      return arg_error("rows out of range");
+    if (rows[i] > 0 && (!pools[i] || n_pool[i] <= 0)) return arg_error("empty pool");
+    if (labels[i] != 0 && labels[i] != 1) return arg_error("label must be 0 or 1");
+    if (rows[i] > 0 && !counts[i]) return arg_error("counts is NULL");
+    seg[i] = EvalSeg{pools[i], n_pool[i], rows[i], row_offsets[i], seeds[i], counts[i], labels[i]};
+    max_rows = std::max(max_rows, rows[i]);
+  }
+  if (ws_bytes < mlp_eval_ws_floats(*p, max_rows) * int64_t(sizeof(float))) return arg_error("workspace too small");
+  return mlp_eval_count_multi(*p, params, pools_are_f16 != 0, seg, n_pools, activation_threshold, dropout_p,
+                              static_cast<float*>(workspace), as_stream(stream));
+}
+
+int hbk_mlp_eval_finish(const float* counts_val, const float* counts_test, const double* sizes,
+                        float target_false_positives_per_hour, float adjust_ratio, float* sched, int64_t sched_len,
+                        int64_t next_step, float* out, void* stream) {
+  using namespace hbk;
+  if (!sizes) return arg_error("sizes is NULL");
+  if (sched && (sched_len <= 0 || next_step < 0)) return arg_error("schedule range");
+  return mlp_eval_finish(counts_val, counts_test, sizes, target_false_positives_per_hour, adjust_ratio, sched,
+                         sched_len, next_step, out, as_stream(stream));
+}
+
+}  // extern "C"

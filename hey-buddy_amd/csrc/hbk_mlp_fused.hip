@@ -50,6 +50,10 @@
 //              hbk_mlp_gate.h: k4's rule on k4's words) and leave before any work,
 //              and k4 decides first and then only zeroes what k2 added to the bucket
 //
+// The step's entry points are at the end of this file, argument checks included:
+// hbk_mlp_fused_supported, hbk_mlp_step_variant, hbk_mlp_step_plan_info,
+// hbk_mlp_step_fwd_bwd, hbk_mlp_step_update. hbk_mlp_forward (hbk_mlp.hip) reaches
+// mlp_fused_run for the inference forward of a plan this file covers.
 // Where the rest lives: hbk_mlp_plan.h, the step's planning as pure host C++ (the
 // variant, every kernel's geometry, the job tables' shapes, the workspace layout,
 // the environment knobs); hbk_mlp_dev.h, the device helpers shared with
@@ -87,6 +91,7 @@ namespace hbk {
 namespace {
 
 constexpr int kStats = 8;
+constexpr int kStepPlanInfo = 19;  // fields of hbk_mlp_step_plan_info
 
 #ifdef HBK_TRACE
 // Tracing build only (lib/libhbk_trace.so, tools/probe_mlp.py): lane 0 of every
@@ -2687,20 +2692,16 @@ int64_t mlp_fused_ws_floats(const hbk_mlp_plan& p, int64_t B) {
   return fused_layout(std::max<int64_t>(B, 1), static_cast<int>(p.g.size()), p.n_params).total;
 }
 
-int mlp_fused_step_variant(int64_t B, hipStream_t s) {
-  return step_v2(B, persistent_blocks(1, s), read_step_knobs()) ? 2 : 1;  // (plan_step's variant)
-}
-
-void mlp_fused_step_plan_info(const hbk_mlp_plan& p, int64_t B, hipStream_t s, int32_t info[kStepPlanInfo]) {
-  const int64_t cus = persistent_blocks(1, s);
-  const int NG = static_cast<int>(p.g.size());
-  const StepPlan pl = plan_step(static_cast<int>(B), NG, p.n_params, cus, read_step_knobs());  // (as mlp_fused_run)
-  const bool v2 = pl.variant == 2;
-  const int32_t f[kStepPlanInfo] = {pl.variant, static_cast<int32_t>(pl.Bp), pl.rt, pl.KS, pl.k1_grid, pl.k1c.KC,
-                                    pl.k1c.RT, v2 ? pl.k3s_pair : -1, v2 ? kK3sPairs[pl.k3s_pair][0] : 0,
-                                    v2 ? kK3sPairs[pl.k3s_pair][1] : 0, pl.S0, pl.S1, pl.sparse, pl.slabs,
-                                    pl.pre_tiles, pl.k3_rows, pl.k3_narrow, NG, static_cast<int32_t>(cus)};
-  std::copy(f, f + kStepPlanInfo, info);
+// fused-only entry points (here and in hbk_mlp_eval.hip) on a plan they do not cover
+int mlp_unsupported(const hbk_mlp_plan& p, const char* what) {
+  if (p.half.n_half > 0)
+    set_error("hbk: %s does not cover half layers (use hbk_mlp_forward / hbk_mlp_train_fwd_bwd)", what);
+  else if (!p.default_block())
+    set_error("hbk: %s covers the gated SiLU MLP only, not a plain MLP or another activation (use "
+              "hbk_mlp_forward / hbk_mlp_train_fwd_bwd)", what);
+  else
+    set_error("hbk: %s covers d_in 1536, layer 96, hidden 64, <= 4 layers", what);
+  return HBK_ERR_UNSUPPORTED;
 }
 
 WCacheOffsets mlp_wcache_offsets(const hbk_mlp_plan& p) {
@@ -2794,9 +2795,10 @@ int mlp_fused_run(const hbk_mlp_plan& p, const float* params, const float* pool3
   return rc == HBK_OK ? finish_partials(r) : rc;
 }
 
-int mlp_fused_update(const hbk_mlp_plan& p, float* params, float* bucket, float* m, float* v, float* state,
-                     int parity, const float* sched, int sched_len, float lr, float b1, float b2, float eps,
-                     float* hist, int hist_cap, float* ws, hipStream_t s) {
+// The update half of a step (hbk_mlp_step_update, below): k4 over the plan's parameters.
+static int fused_update(const hbk_mlp_plan& p, float* params, float* bucket, float* m, float* v, float* state,
+                        int parity, const float* sched, int sched_len, float lr, float b1, float b2, float eps,
+                        float* hist, int hist_cap, float* ws, hipStream_t s) {
   if (p.deferred_ws && p.deferred_ws != ws) {
     set_error("hbk: the previous hbk_mlp_step_fwd_bwd deferred its weight-gradient partials to its workspace: "
               "pass that workspace to hbk_mlp_step_update");
@@ -2859,6 +2861,93 @@ int mlp_fused_update(const hbk_mlp_plan& p, float* params, float* bucket, float*
 }
 
 }  // namespace hbk
+
+// The train step's entry points: argument checks, then the launchers above.
+extern "C" {
+
+int hbk_mlp_fused_supported(const hbk_mlp_plan* p, int32_t* supported) {
+  if (!p || !supported) return hbk::arg_error("NULL");
+  *supported = hbk::mlp_fused_supported(*p) ? 1 : 0;
+  return HBK_OK;
+}
+
+int hbk_mlp_step_variant(const hbk_mlp_plan* p, int64_t batch, void* stream, int32_t* variant) {
+  using namespace hbk;
+  if (!p || !variant) return arg_error("NULL");
+  if (!mlp_fused_supported(*p)) return mlp_unsupported(*p, "the fused train step");
+  if (batch <= 0 || batch > (1 << 22)) return arg_error("batch out of range");
+  *variant = step_v2(batch, persistent_blocks(1, as_stream(stream)), read_step_knobs()) ? 2 : 1;  // (plan_step's)
+  return HBK_OK;
+}
+
+// The plan mlp_fused_run takes for batch rows on the stream, as kStepPlanInfo fields; launches nothing
+int hbk_mlp_step_plan_info(const hbk_mlp_plan* p, int64_t batch, void* stream, int32_t* info, int32_t n_info) {
+  using namespace hbk;
+  if (!p || !info) return arg_error("NULL");
+  if (!mlp_fused_supported(*p)) return mlp_unsupported(*p, "the fused train step");
+  if (batch <= 0 || batch > (1 << 22)) return arg_error("batch out of range");
+  if (n_info < kStepPlanInfo) return arg_error("hbk_mlp_step_plan_info: info holds fewer than 19 fields");
+  const int64_t cus = persistent_blocks(1, as_stream(stream));
+  const int NG = static_cast<int>(p->g.size());
+  const StepPlan pl = plan_step(static_cast<int>(batch), NG, p->n_params, cus, read_step_knobs());  // (as mlp_fused_run)
+  const bool v2 = pl.variant == 2;
+  const int32_t f[kStepPlanInfo] = {pl.variant, static_cast<int32_t>(pl.Bp), pl.rt, pl.KS, pl.k1_grid, pl.k1c.KC,
+                                    pl.k1c.RT, v2 ? pl.k3s_pair : -1, v2 ? kK3sPairs[pl.k3s_pair][0] : 0,
+                                    v2 ? kK3sPairs[pl.k3s_pair][1] : 0, pl.S0, pl.S1, pl.sparse, pl.slabs,
+                                    pl.pre_tiles, pl.k3_rows, pl.k3_narrow, NG, static_cast<int32_t>(cus)};
+  std::copy(f, f + kStepPlanInfo, info);
+  return HBK_OK;
+}
+
+int hbk_mlp_step_fwd_bwd(const hbk_mlp_plan* p, const float* params, const float* pool32, int64_t n32,
+                         const void* pool16, int64_t n16, const int32_t* idx, int64_t idx_step_stride, const float* y, int64_t y_step_stride,
+                         int64_t batch, const float* state, int32_t parity, const float* sched, int64_t sched_len,
+                         float neg_weight, float high_loss_threshold, float activation_threshold, float dropout_p,
+                         uint64_t seed, float* bucket, float* prob, int64_t idx_steps, int32_t flags,
+                         void* workspace, int64_t ws_bytes, void* stream) {
+  using namespace hbk;
+  if (!p) return arg_error("plan is NULL");
+  if (!mlp_fused_supported(*p)) return mlp_unsupported(*p, "the fused train step");
+  if (batch <= 0 || batch > (1 << 22)) return arg_error("batch out of range");
+  if (!params || !y || !bucket || !workspace || !state) return arg_error("NULL pointer");
+  if (!idx && !pool32) return arg_error("no rows: idx and pool32 are NULL");
+  if (parity != 0 && parity != 1) return arg_error("parity must be 0 or 1");
+  if (sched && sched_len <= 0) return arg_error("sched_len must be > 0");
+  if (dropout_p < 0.f || dropout_p >= 1.f) return arg_error("dropout_p must be in [0, 1)");
+  if (ws_bytes < mlp_fused_ws_floats(*p, batch) * int64_t(sizeof(float))) return arg_error("workspace too small");
+  if (n32 < 0 || n16 < 0) return arg_error("negative pool size");
+  if (!idx && n32 < batch) return arg_error("idx NULL: pool32 must hold the batch rows");
+  if (flags & ~(HBK_STEP_XHAT_READY | HBK_STEP_PREFETCH_NEXT | HBK_STEP_WEIGHTS_READY | HBK_STEP_DEFER_PARTIALS |
+                HBK_STEP_GATE_SKIP))
+    return arg_error("unknown flags");
+  if ((flags & HBK_STEP_GATE_SKIP) && !(flags & HBK_STEP_DEFER_PARTIALS))
+    return arg_error("HBK_STEP_GATE_SKIP needs HBK_STEP_DEFER_PARTIALS (the update that follows must own the slabs)");
+  if (!pool32 && !pool16) return arg_error("no embedding pool");
+  return mlp_fused_run(*p, params, pool32, n32, pool16, n16, idx, idx_step_stride, idx_steps, y, y_step_stride,
+                       static_cast<int>(batch), state, parity, sched,
+                       static_cast<int>(std::min<int64_t>(sched_len, 1 << 30)), neg_weight, high_loss_threshold,
+                       activation_threshold, dropout_p, seed, bucket, prob, nullptr, static_cast<float*>(workspace),
+                       true, flags, as_stream(stream));
+}
+
+int hbk_mlp_step_update(const hbk_mlp_plan* p, float* params, float* bucket, float* m, float* v, float* state,
+                        int32_t parity, const float* sched, int64_t sched_len, float lr, float beta1, float beta2,
+                        float eps, float* history, int32_t history_cap, void* workspace, int64_t ws_bytes,
+                        void* stream) {
+  using namespace hbk;
+  if (!p) return arg_error("plan is NULL");
+  if (!p->default_block()) return mlp_unsupported(*p, "the fused train step");
+  if (!params || !bucket || !m || !v || !state) return arg_error("NULL pointer");
+  if (parity != 0 && parity != 1) return arg_error("parity must be 0 or 1");
+  if (sched && sched_len <= 0) return arg_error("sched_len must be > 0");
+  if (workspace && (!mlp_fused_supported(*p) || ws_bytes < mlp_fused_ws_floats(*p, 1) * int64_t(sizeof(float))))
+    return arg_error("workspace: fused plans only, and at least the weight cache");
+  return fused_update(*p, params, bucket, m, v, state, parity, sched,
+                      static_cast<int>(std::min<int64_t>(sched_len, 1 << 30)), lr, beta1, beta2, eps, history,
+                      history ? history_cap : 0, static_cast<float*>(workspace), as_stream(stream));
+}
+
+}  // extern "C"
 
 #ifdef HBK_BOUNDS
 extern "C" int hbk_debug_bounds(unsigned long long* out) {

@@ -19,7 +19,7 @@
 //                      the products below hash no element again
 //   half_hg_kernel     HG_h = Xn_h W_hg_h^T + b_hg_h over (row tile, column tile, branch);
 //                      Xn is rebuilt from x and the statistics while staging, never stored
-//   half_gate_kernel   U = silu(H) * G
+//   gate_fwd_kernel    U = silu(H) * G over [B n_half, H]: the generic path's kernel (mlp_gate_forward)
 //   half_out_kernel    part_h = U_h W_o_h^T over (row tile, column tile, branch): the GEMM of depth
 //                      n_half * H over [U_0 .. U_{n-1}], its depth split by branch
 //   half_sum_kernel    s0 += sum_h (part_h + b_o_h), branches in order
@@ -38,7 +38,6 @@ namespace {
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 
-constexpr float kLnEps = 1e-5f;
 constexpr int TM = kHalfTile, TN = kHalfTile, TK = kHalfTileK;
 
 // what the kernels need of the plan, by value
@@ -58,13 +57,11 @@ __device__ __forceinline__ Drop make_drop(float p, uint64_t seed, const double* 
   return Drop{p, p > 0.f ? 1.f / (1.f - p) : 1.f, seed};
 }
 
-// element (row, col) of the dropped-out input: the mask of hbk_mlp.hip's dropped(), a function
-// of the element's place in the ungathered row, so every branch and norm_in see one mask
+// element (row, col) of the dropped-out input (dropout_elem): the mask is a function of the
+// element's place in the ungathered row, so every branch and norm_in see one mask
 __device__ __forceinline__ float xval(const float* __restrict__ x, int64_t row, int col, int d_in, const Drop& d) {
   const int64_t e = row * d_in + col;
-  const float v = x[e];
-  if (d.p <= 0.f) return v;
-  return uniform01(d.seed, static_cast<uint64_t>(e)) < d.p ? 0.f : v * d.ks;
+  return dropout_elem(x[e], d.seed, static_cast<uint64_t>(e), d.p, d.ks);
 }
 
 // gathered column c of branch h -> column of the flattened row
@@ -72,14 +69,6 @@ __device__ __forceinline__ int src_col(const HalfDev& hd, int h, int c) {
   const int t = c / hd.chunk;
   return hd.tok[h * hd.per + t] * hd.chunk + (c - t * hd.chunk);
 }
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
 // One 64 x 64 output tile, 4 waves as 2 x 2 of 32 x 32, over k in [kb, ke): acc += A B with
 // A(m, k) = la(m, k), B(k, n) = lb(n, k), m / n tile-local; the loaders return 0 outside their
@@ -245,17 +234,6 @@ __global__ void __launch_bounds__(256) half_hg_kernel(HalfDev hd, const float* _
         const int64_t row = m0 + ln.m(i, q);
         if (row < rows) hg[(row * hd.nh + h) * N + n] = acc[i][j][q] + bb;
       }
-  }
-}
-
-// U = silu(H) * G over [rows = B n_half, H]
-__global__ void half_gate_kernel(const float* __restrict__ hg, float* __restrict__ u, int64_t rows, int H) {
-  const int64_t n = rows * H;
-  for (int64_t e = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; e < n; e += int64_t(gridDim.x) * blockDim.x) {
-    const int64_t r = e / H;
-    const int j = static_cast<int>(e - r * H);
-    const float hv = hg[r * 2 * H + j], gv = hg[r * 2 * H + H + j];
-    u[e] = hv * sigmoidf_(hv) * gv;
   }
 }
 
@@ -501,8 +479,9 @@ int mlp_half_forward(const hbk_mlp_plan& p, const float* params, const float* x,
   HBK_LAUNCH_CHECK("half_stats_kernel");
   hipLaunchKernelGGL(half_hg_kernel, d3(g.hg), dim3(256), 0, s, hd, params, xs, ws + w.stats, ws + w.hg, B);
   HBK_LAUNCH_CHECK("half_hg_kernel");
-  hipLaunchKernelGGL(half_gate_kernel, d3(g.gate), dim3(256), 0, s, ws + w.hg, ws + w.u, int64_t(B) * hd.nh, hd.H);
-  HBK_LAUNCH_CHECK("half_gate_kernel");
+  // (B n_half <= 2^20 * 256 rows: hbk_mlp_forward / hbk_mlp_train_fwd_bwd bound a half plan's batch)
+  const int rc = mlp_gate_forward(ws + w.hg, ws + w.u, B * hd.nh, hd.H, s);
+  if (rc != HBK_OK) return rc;
   hipLaunchKernelGGL(half_out_kernel, d3(g.out), dim3(256), 0, s, hd, params, ws + w.u, ws + w.part, B);
   HBK_LAUNCH_CHECK("half_out_kernel");
   hipLaunchKernelGGL(half_sum_kernel, d3(g.sum), dim3(256), 0, s, hd, params, ws + w.part, s0, int64_t(B));

@@ -95,7 +95,7 @@ struct HalfGrid {
 struct HalfGrids {
   HalfGrid stats;  // one workgroup per row
   HalfGrid hg;     // HG_h = Xn_h W_hg_h^T: (2 hid, B, n_half)
-  HalfGrid gate;   // element-wise over [B n_half, hid]
+  HalfGrid gate;   // element-wise over [B n_half, hid]: what mlp_gate_forward launches gate_fwd_kernel with
   HalfGrid out;    // part_h = U_h W_o_h^T: (layer, B, n_half)
   HalfGrid sum;    // s0 += sum_h part_h + b_o_h: element-wise over [B, layer]
   HalfGrid dwo;    // dW_o = dS0^T U: (n_half hid, layer, batch splits)

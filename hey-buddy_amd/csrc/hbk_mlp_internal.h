@@ -1,40 +1,28 @@
-// The classifier plan shared by hbk_mlp.hip (generic GEMM path, any dims) and the
-// fused path for the default architecture: hbk_mlp_fused.hip (train step) and
-// hbk_mlp_eval.hip (evaluation passes).
+// What the classifier's translation units share. hbk_mlp.hip: the generic GEMM path (any dims), the
+// plan constructors and its entry points; hbk_mlp_act.hip: the activation step of plans other than
+// gated SiLU; hbk_mlp_half.hip: the half-layer bank; hbk_mlp_fused.hip: the fused train step of the
+// default architecture; hbk_mlp_eval.hip: its evaluation passes. Every extern "C" entry point lives
+// beside the kernels it launches, so only these cross a unit: the plan itself, the device helpers
+// that hbk_mlp.hip and hbk_mlp_half.hip both use, the activation, gate and half-bank calls of the
+// generic forward / backward, the three fused calls behind hbk_mlp_forward / hbk_mlp_workspace_size,
+// and the weight cache the evaluation unit borrows from the train step.
+// The host-only geometry is in hbk_mlp_layout.h (generic path), hbk_mlp_half_plan.h (bank) and
+// hbk_mlp_plan.h (fused step).
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <algorithm>
 #include <vector>
 
 #include "hbk_mlp_act.h"
 #include "hbk_mlp_dims.h"
 #include "hbk_mlp_half_plan.h"
+#include "hbk_mlp_layout.h"
 
-namespace hbk {
-
-struct Gmlp {
-  int in, hid, out;
-  int64_t w_hg, b_hg, w_o, b_o;  // float offsets into the flat parameter buffer
-  // rows of W_hg = columns of HG: 2 hid (hidden rows then gate rows), or hid in a plain plan
-  // (hbk_mlp_plan_create_ex with gated = 0: W_hg / b_hg are hidden.weight / hidden.bias alone)
-  int wid = 0;
-};
-struct Ln {
-  int d;
-  int64_t g, b;
-};
-
-}  // namespace hbk
-
-struct hbk_mlp_plan {
+// ln_in, g, ln, n_params: hbk_mlp_layout.h (a half plan's n_params also counts the bank)
+struct hbk_mlp_plan : hbk::MlpParams {
   int d_in = 0, layer = 0, hid = 0, n_layers = 0;
-  hbk::Ln ln_in;
-  std::vector<hbk::Gmlp> g;  // mlp_in, layers..., mlp_out
-  std::vector<hbk::Ln> ln;   // layers' LNs..., norm_out
-  int64_t n_params = 0;
   // hbk_mlp_plan_create_ex: MultiLayerPerceptron blocks (no gate) when false; the activation
   // (HBK_ACT_*). Gated SiLU is the default architecture, the only one the fused kernels, the
   // evaluation passes and the half-layer bank cover.
@@ -77,8 +65,26 @@ __device__ __forceinline__ float adam_step(float mi, float vi, float step_size, 
   return step_size * mi * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(vi) * inv_bc2s + eps);
 }
 
-// Grid of an elementwise grid-stride kernel over n elements, 256 threads per block
-inline unsigned mlp_ew_grid(int64_t n) { return static_cast<unsigned>(std::min<int64_t>((n + 255) / 256, 4096)); }
+// The three helpers below are shared by hbk_mlp.hip and hbk_mlp_half.hip (the fused units have
+// their own forms in hbk_mlp_dev.h: another reduction order, other instructions, other bits).
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
+
+// Input dropout (nn.Dropout, wakeword.py:197/338: zero with prob p, scale by 1/(1-p)) of the value v
+// at element e of the flattened [B, d_in] input: norm_in and every half-layer branch see one mask.
+__device__ __forceinline__ float dropout_elem(float v, uint64_t seed, uint64_t e, float p, float keep_scale) {
+  if (p <= 0.f) return v;
+  return uniform01(seed, e) < p ? 0.f : v * keep_scale;
+}
+
+// fused-only entry points on a plan they do not cover: sets the message, returns HBK_ERR_UNSUPPORTED
+// (hbk_mlp_fused.hip)
+int mlp_unsupported(const hbk_mlp_plan& p, const char* what);
 
 // The activation step of one MLP block for any (HBK_ACT_*, gated) pair (hbk_mlp_act.hip).
 // Forward: u [rows, H] = f(H) (* G) from hg [rows, gated ? 2H : H]; backward: dhg of hg's shape
@@ -86,32 +92,30 @@ inline unsigned mlp_ew_grid(int64_t n) { return static_cast<unsigned>(std::min<i
 int mlp_act_forward(int act, bool gated, const float* hg, float* u, int rows, int H, hipStream_t s);
 int mlp_act_backward(int act, bool gated, const float* du, const float* hg, float* dhg, int rows, int H,
                      hipStream_t s);
+// The gated SiLU block's own forward, u [rows, H] = silu(H) * G from hg [rows, 2H] (gate_fwd_kernel in
+// hbk_mlp.hip), which the half-layer bank runs over its [B n_half, H] too.
+int mlp_gate_forward(const float* hg, float* u, int rows, int H, hipStream_t s);
 
 // True when the fused kernels (train step: hbk_mlp_fused.hip; evaluation passes:
 // hbk_mlp_eval.hip) cover this plan.
 bool mlp_fused_supported(const hbk_mlp_plan& p);
-// The weight cache both read (f16 hi / lo planes of W_o_k, k < NG - 1, and W_hg_k, k >= 1, as
-// stored and transposed; hbk_mlp_dev.h: WSplit): its planes' offsets in halves from the cache
-// base, and its fill from the parameters (k0_wsplit_kernel, in hbk_mlp_fused.hip)
-struct WCacheOffsets {
-  int64_t c_o[kMaxG], c_oT[kMaxG], c_hg[kMaxG], c_hgT[kMaxG];
-};
-WCacheOffsets mlp_wcache_offsets(const hbk_mlp_plan& p);
-int mlp_wcache_fill(const hbk_mlp_plan& p, const float* params, float* cache, hipStream_t s);
+// hbk_mlp_forward on such a plan (train = false) and hbk_mlp_step_fwd_bwd: hbk_mlp_fused.hip
 int64_t mlp_fused_ws_floats(const hbk_mlp_plan& p, int64_t B);
-// 1 (k1a / k1b / k3) or 2 (k1s / k1c / k3s): the train step mlp_fused_run takes for B rows on s
-int mlp_fused_step_variant(int64_t B, hipStream_t s);
-// The plan mlp_fused_run takes for B rows on s (hbk_mlp_step_plan_info's fields); launches nothing
-constexpr int kStepPlanInfo = 19;
-void mlp_fused_step_plan_info(const hbk_mlp_plan& p, int64_t B, hipStream_t s, int32_t info[kStepPlanInfo]);
 int mlp_fused_run(const hbk_mlp_plan& p, const float* params, const float* pool32, int64_t n32,
                   const void* pool16, int64_t n16, const int32_t* idx, int64_t idx_stride, int64_t idx_steps,
                   const float* y, int64_t y_stride, int B, const float* state, int parity, const float* sched,
                   int sched_len, float neg_weight, float thr, float act_thr, float drop_p, uint64_t seed,
                   float* bucket, float* prob, float* logit, float* ws, bool train, int flags, hipStream_t s);
-int mlp_fused_update(const hbk_mlp_plan& p, float* params, float* bucket, float* m, float* v, float* state,
-                     int parity, const float* sched, int sched_len, float lr, float b1, float b2, float eps,
-                     float* hist, int hist_cap, float* ws, hipStream_t s);
+// The weight cache the train step and the evaluation passes read (f16 hi / lo planes of W_o_k,
+// k < NG - 1, and W_hg_k, k >= 1, as stored and transposed; hbk_mlp_dev.h: WSplit): its planes'
+// offsets in halves from the cache base, and its fill from the parameters (k0_wsplit_kernel, in
+// hbk_mlp_fused.hip)
+struct WCacheOffsets {
+  int64_t c_o[kMaxG], c_oT[kMaxG], c_hg[kMaxG], c_hgT[kMaxG];
+};
+WCacheOffsets mlp_wcache_offsets(const hbk_mlp_plan& p);
+int mlp_wcache_fill(const hbk_mlp_plan& p, const float* params, float* cache, hipStream_t s);
+
 // Half-layer bank (hbk_mlp_half.hip), called from the generic forward / backward of hbk_mlp.hip.
 // ws: the bank's workspace (half_ws_layout). Forward: s0 [B, layer] += sum_h branch_h(x) and keeps
 // statistics, HG, U and (drop_p > 0) the dropped-out input; backward, after that forward on the same ws
@@ -120,25 +124,4 @@ int mlp_half_forward(const hbk_mlp_plan& p, const float* params, const float* x,
                      float drop_p, uint64_t seed, const double* step_sc, hipStream_t s);
 int mlp_half_backward(const hbk_mlp_plan& p, const float* params, const float* x, int B, const float* ds0,
                       float* G, float* ws, float drop_p, hipStream_t s);
-// Evaluation passes (validation / testing forwards reduced to prediction counts)
-int64_t mlp_eval_ws_floats(const hbk_mlp_plan& p, int64_t rows);
-int mlp_eval_prepare(const hbk_mlp_plan& p, const float* params, float* ws, hipStream_t s);
-int mlp_eval_count(const hbk_mlp_plan& p, const float* params, const void* pool, bool f16, int64_t n_pool,
-                   const int32_t* idx, int64_t rows, int64_t r0, int label, float act_thr, float drop_p,
-                   uint64_t seed, float* counts, float* prob, float* ws, hipStream_t s);
-// the rows mlp_eval_count evaluates in the lap form (two laps of the pool together) and in the plain form
-void mlp_eval_lap_plan(int64_t rows, int64_t n_pool, bool f16, bool has_idx, int64_t part[2]);
-// one pool of an evaluation launch (mlp_eval_count_multi: several pools of one dtype in one launch)
-struct EvalSeg {
-  const void* pool;
-  int64_t n_pool, rows, r0;
-  uint64_t seed;
-  float* counts;
-  int label;
-};
-constexpr int kEvalMaxSeg = 4;
-int mlp_eval_count_multi(const hbk_mlp_plan& p, const float* params, bool f16, const EvalSeg* seg, int nseg,
-                         float act_thr, float drop_p, float* ws, hipStream_t s);
-int mlp_eval_finish(const float* cv, const float* ct, const double* sizes, float target, float ratio, float* sched,
-                    int64_t sched_len, int64_t next_step, float* out, hipStream_t s);
 }  // namespace hbk

@@ -252,8 +252,8 @@ def bucket(params, x, y, neg_weight=1.0, threshold=1e-4):
 
 
 def generic_dropout_keep(seed: int, n_rows: int, d: int = 1536, p: float = 0.1) -> np.ndarray:
-    """The input-dropout mask of the generic classifier kernels (dropped() in hbk_mlp.hip,
-    uniform01 in hbk_mlp_internal.h, which the half-layer kernels share): element i = row d + column
+    """The input-dropout mask of the generic classifier kernels (dropout_elem and
+    uniform01 in hbk_mlp_internal.h, which hbk_mlp.hip and the half-layer kernels share): element i = row d + column
     of the UNGATHERED input is dropped iff the top 24 bits of splitmix64(seed + golden (i + 1)),
     as a float32 in [0, 1), are below p. [n_rows, d] bool, True = kept. (oracle.mlp.dropout_keep
     restates the fused kernels' 16-bit hash, which this path does not use.)"""
