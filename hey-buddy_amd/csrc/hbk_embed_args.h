@@ -1,6 +1,7 @@
 // Kernel-argument structs and geometry constants of the speech-embedding conv
-// stack, shared by the kernels (hbk_embed.hip) and the host planner
-// (hbk_embed_plan.h). Plain C++17, no HIP header: the planner and its check
+// stack, shared by the kernels (hbk_embed_exact.hip, hbk_embed_x3.hip,
+// hbk_embed_band.hip, hbk_embed_stream.hip), their launcher (hbk_embed.hip) and
+// the host planner (hbk_embed_plan.h). Plain C++17, no HIP header: the planner and its check
 // (tests/embed_plan_check.cpp) build for the CPU. The unnamed namespace is part
 // of the kernels' mangled names (their parameters are these structs), so it stays.
 #pragma once

@@ -4,7 +4,8 @@
 // weight / bias / table bytes and the launch geometry — and every planning
 // error, before any device call. Plain C++17 over hbk_embed_args.h and the
 // standard library: no HIP, no environment, no output. hbk_embed.hip realises a
-// plan on the device; tests/embed_plan_check.cpp runs this header on the CPU.
+// plan on the device (the kernels a KernelChoice names are in the family units,
+// hbk_embed_internal.h); tests/embed_plan_check.cpp runs this header on the CPU.
 #pragma once
 
 #include <algorithm>
@@ -28,7 +29,7 @@ namespace {
 constexpr int kPlanOk = 0, kPlanErrArg = -1, kPlanErrUnsupported = -3;
 constexpr int kOpConv = 0, kOpMaxPool = 1;
 
-// The environment of one plan creation (read_embed_knobs in hbk_embed.hip).
+// The environment of one plan creation (read_embed_knobs in hbk_embed.hip, the host unit).
 struct EmbedKnobs {
   bool lds_kb_set = false;  // HBK_EMBED_LDS_KB: LDS per block of the split-f16 kernel (16 .. 160), for tuning
   int lds_kb = 0;

@@ -3,7 +3,8 @@
 // Arguments: graph files (written by the test). For every graph, precision and knob set
 // of the case list it plans, asserts the plan's invariants and prints the plan as scalars
 // and hashes; the test compares the output with the table recorded from the tree before
-// the planner was split out of hbk_embed.hip (tests/golden/embed_plan_parent.json).
+// the planner was split out of hbk_embed.hip, then the stack's one unit
+// (tests/golden/embed_plan_parent.json).
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>

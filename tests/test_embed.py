@@ -282,7 +282,7 @@ def test_embed_split_precision_margin():
 @pytest.mark.gpu
 def test_featurize_across_the_16384_clip_chunk():
     """hbk_embed_clips works through the batch in 16,384-clip workspace chunks
-    (hbk_embed.hip kChunkClips): 16,390 clips cross one boundary. The clips on
+    (kChunkClips in hbk_embed.hip, the stack's host unit): 16,390 clips cross one boundary. The clips on
     both sides of it (and the first / last) against the oracle mel + graph."""
     from heybuddy.embedding_graph import se20_graph
     from heybuddy.embeddings import SpeechEmbeddings

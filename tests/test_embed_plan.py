@@ -10,7 +10,7 @@ offsets inside their blob; gather indices below n_src; workspace buffers that
 hold every chain's output; positive task counts) and prints every plan: kernel
 values, the scalar fields of the argument structs, launch geometry and a hash
 of each packed blob. The output must equal, exactly, the table recorded from the
-tree before the planner was split out of hbk_embed.hip
+tree before the planner was split out of hbk_embed.hip (then the stack's one unit)
 (tests/golden/embed_plan_parent.json; DESIGN.md says how it was made).
 """
 import json
